@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: hash-grid fwd+bwd samples/s (16 levels, F=2) on synthetic point batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, per-operator times, roofline on those times).
+--full adds everything else the line can carry, each leg measured in runs of its own after the timed steps: PSNR fits,
+the fused-Adam pass, stream rates and bound model, the other BASELINE configurations, the CPU baseline and the reference's
+kernels. --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 A "step" = one pass of the hot path over one batch: the forward operator (all 16 levels; it builds the batch's plan -- the
 sample sort -- INSIDE the timed step, every step, into a caller-owned buffer), the backward operator (gradient scatter-add
@@ -137,6 +142,24 @@ def quick_measure(name, device, iters=20):
                             "backward_item_stream_floor_ms": stream_floor,
                             "note": "floors of the binding resources (L2->L1 lines of the fine levels; 64-bit LDS atomics at "
                                     "2.3 T/s; item stream written + read at 5.4 TB/s), not of HBM bytes"}}
+
+
+# --dump-outputs: bytes per array (56 MiB in all). A larger output is written as a sample of its rows.
+DUMP_BUDGET = {"features": 8 << 20, "grad_codebook": 48 << 20}
+
+
+def dump_outputs(out_dir, outputs, seed=0):
+    """Writes each tensor of `outputs` (name -> [rows, ...]) as `out_dir/<name>.npy` in float32. One that exceeds its
+    DUMP_BUDGET is replaced by the rows at sorted indices drawn without replacement from numpy's default_rng(seed): the
+    same rows for the same shape, so that two builds run with the same arguments can be compared row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().float()
+        rows = max(1, DUMP_BUDGET[name] // (4 * max(1, t[0].numel())))
+        if t.shape[0] > rows:
+            idx = np.sort(np.random.default_rng(seed).choice(t.shape[0], rows, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def kernel_source_hash():
@@ -471,6 +494,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)     # SURVEY 8(d) protocol: 20 warm-up + 100 timed iterations
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the secondary legs of the line (PSNR fits, fused Adam, stream "
+                         "rates and bound model, other BASELINE configurations, CPU baseline, the reference's kernels); "
+                         "the --psnr-steps / --nerf-steps / --no-secondary / --no-cpu-baseline / --cpu-* options steer them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (forward features, codebook gradient) as DIR/<name>.npy, "
+                         "float32; larger ones as a fixed sample of their rows (dump_outputs)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, the driver's contract): the workload's samples PER GPU; strong: the same total "
                          "split over the ranks")
@@ -507,6 +537,8 @@ def main():
                     help="only exercise the multi-rank launch (spawn, rendezvous, one all-reduce, JSON line with n_gpus); "
                          "needs no GPU: ranks use the gloo backend. The metric value is null.")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N launched plainly (no torchrun environment): start the N rank processes ourselves, BEFORE anything in this
     # process touches the GPU (a process that has initialised HIP must never be replaced or forked into ranks); this
@@ -605,8 +637,9 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
-    for k in range(args.steps):
+    for k in range(args.steps - 1):
         step(events[k])
+    last = step(events[-1])     # kept only from the last step, so that every step allocates as before
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
@@ -614,12 +647,15 @@ def main():
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"features": last[0], "grad_codebook": last[1]})
+    del last
 
     # PSNR at a fixed step (second half of BASELINE.json's metric): config-B LatentGrid (16-level 2-D, F=2, latent
     # quantisation + entropy model on) fitted to a 512x768 procedural image, pixels sharded over the ranks with one
     # gradient all-reduce per step; OUTSIDE the timed throughput region.
     psnr = None
-    if args.psnr_steps > 0:
+    if args.full and args.psnr_steps > 0:
         from shacira_amd import harness
         torch.cuda.synchronize()
         tp = time.perf_counter()
@@ -644,7 +680,7 @@ def main():
     # second PSNR figure (rank 0 only, outside the timed region): the reference's per-step NeRF pipeline -- ray marching
     # on the occupancy grid, hash-grid lookup, MFMA decoders, volume integration, L1, fused Adam -- on a closed-form scene
     psnr_nerf = None
-    if rank == 0 and args.nerf_steps > 0:
+    if rank == 0 and args.full and args.nerf_steps > 0:
         from shacira_amd import harness
         torch.cuda.synchronize()
         tp = time.perf_counter()
@@ -680,7 +716,7 @@ def main():
 
     # the optimiser pass that follows the backward in training (SURVEY 8d "second figure"): fused Adam over the table
     ms_adam = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from shacira_amd.optim import FusedAdam
         ptab = torch.nn.Parameter(table.clone())
         ptab.grad = torch.randn_like(ptab)
@@ -697,7 +733,7 @@ def main():
         del ptab, opt
 
     secondary = None
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and args.full and not args.no_secondary:
         st.clear()
         del coords, grad_out, step
         torch.cuda.empty_cache()
@@ -733,71 +769,73 @@ def main():
             else:
                 traffic_source = (f"none: profiles/{os.path.basename(tpath)} was measured on other kernel sources "
                                   f"({rec.get('kernel_source_hash')} != {kernel_source_hash()})")
-        traffic = traffic_bwd if dom[0] == "backward" else traffic_fwd
-        # what this chip's memory system sustains on plain streams, measured in the same run (SURVEY 8d asks for the
-        # nominal AND the measured peak): a 1 GiB device-to-device copy (read + write), a fill (write only) and a
-        # reduction (read only), bytes moved / time. The nominal 8 TB/s stays the `peak` of the contract.
-        def stream_gbs(fn, nbytes, it=5):
-            fn()
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(it):
+        measured = bound_model = None
+        if args.full:
+            traffic = traffic_bwd if dom[0] == "backward" else traffic_fwd
+            # what this chip's memory system sustains on plain streams, measured in the same run (SURVEY 8d asks for the
+            # nominal AND the measured peak): a 1 GiB device-to-device copy (read + write), a fill (write only) and a
+            # reduction (read only), bytes moved / time. The nominal 8 TB/s stays the `peak` of the contract.
+            def stream_gbs(fn, nbytes, it=5):
                 fn()
-            b.record()
-            torch.cuda.synchronize()
-            return nbytes * it / (a.elapsed_time(b) * 1e-3) / 1e9
-        src = torch.empty(1 << 28, dtype=torch.float32, device=device).normal_()
-        dst = torch.empty_like(src)
-        nb = src.numel() * 4
-        Lh = _lib.lib()
-        strm = torch.cuda.current_stream(device).cuda_stream
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(it):
+                    fn()
+                b.record()
+                torch.cuda.synchronize()
+                return nbytes * it / (a.elapsed_time(b) * 1e-3) / 1e9
+            src = torch.empty(1 << 28, dtype=torch.float32, device=device).normal_()
+            dst = torch.empty_like(src)
+            nb = src.numel() * 4
+            Lh = _lib.lib()
+            strm = torch.cuda.current_stream(device).cuda_stream
 
-        def probe(kind):
-            _lib.check(Lh.shacira_stream_probe(kind, src.data_ptr(), dst.data_ptr(), nb, strm), "stream_probe")
-        measured = {"copy_read+write": stream_gbs(lambda: probe(2), 2 * nb),
-                    "write_only": stream_gbs(lambda: probe(1), nb),
-                    "read_only": stream_gbs(lambda: probe(0), nb),
-                    "torch_copy_read+write": stream_gbs(lambda: dst.copy_(src), 2 * nb),
-                    "unit": "GB/s", "how": "shacira_stream_probe (16 B per lane, 8 in flight, non-temporal: the access shape of "
-                                           "the hash-grid kernels) over 1 GiB, HIP events, 5 repetitions; torch copy_ beside it"}
-        del src, dst
-        if traffic is not None:
-            measured["operator_traffic_over_time_GBps"] = traffic / (dom[1] * 1e-3) / 1e9
-        # What actually binds the two operators on this access pattern: next to the contract's HBM
-        # fraction (algorithmic bytes / 8 TB/s), the floor each operator has on the resource that limits it, and how close
-        # the measured time is to that floor.
-        #  forward: a hashed level's x-pair of corners is one 128-byte line; with uniformly random samples every pair of a
-        #   level finer than the batch's density is its own line, and a CU's L2 -> L1 path moves 64 B/clk: 2 clk per line
-        #   (measured: 38 TCP->TCC requests and 81 TA-busy cycles per gather instruction, profiles/r02_fwd_counters.md).
-        #  backward: the traffic its kernels move (PMC counters, profiles/rNN_pmc_traffic.json; without them: algorithmic
-        #   bytes x the 1.93 measured in round 2) at the copy rate this chip sustains in the same run.
-        n_fine = sum(1 for r in res if float(r) ** dim > 4.0 * n_local) if dim == 3 else 0
-        lines = n_fine * n_local * (2 ** (dim - 1))
-        cus, clk_ghz = 256, 2.4
-        fwd_floor_ms = lines * 2.0 / (cus * clk_ghz * 1e9) * 1e3
-        bwd_traffic = traffic_bwd
-        bwd_bytes = bwd_traffic if bwd_traffic is not None else 1.93 * b_bwd * n_local
-        bwd_floor_ms = bwd_bytes / (measured["copy_read+write"] * 1e9) * 1e3
-        bound_model = {
-            "forward": {"resource": "L2 -> L1 line path of the CUs: 64 B/clk/CU = 2 clk per 128-byte line, 256 CUs at 2.4 GHz",
-                        "what": (f"{n_fine} levels with more than 4 cells per sample (no two samples share a table line in any order; "
-                                 f"the kernel split is another matter: the rows kernel takes levels up to 32 cells per sample) x "
-                                 f"{n_local} samples x {2 ** (dim - 1)} lines (one per x-pair of corners)"),
-                        "ms": fwd_floor_ms, "operator_ms": ms_fwd,
-                        "frac_of_floor": (fwd_floor_ms / ms_fwd) if ms_fwd > 0 else None},
-            "backward": {"resource": "copy rate measured in this run (shacira_stream_probe, read + write)",
-                         "what": ("PMC traffic of the backward's kernels" if bwd_traffic is not None else
-                                  "algorithmic bytes x 1.93 (round-2 PMC ratio; no counters for these kernel sources)"),
-                         "bytes": bwd_bytes, "GBps": measured["copy_read+write"], "ms": bwd_floor_ms, "operator_ms": ms_bwd,
-                         "frac_of_floor": (bwd_floor_ms / ms_bwd) if ms_bwd > 0 else None},
-        }
+            def probe(kind):
+                _lib.check(Lh.shacira_stream_probe(kind, src.data_ptr(), dst.data_ptr(), nb, strm), "stream_probe")
+            measured = {"copy_read+write": stream_gbs(lambda: probe(2), 2 * nb),
+                        "write_only": stream_gbs(lambda: probe(1), nb),
+                        "read_only": stream_gbs(lambda: probe(0), nb),
+                        "torch_copy_read+write": stream_gbs(lambda: dst.copy_(src), 2 * nb),
+                        "unit": "GB/s", "how": "shacira_stream_probe (16 B per lane, 8 in flight, non-temporal: the access shape of "
+                                               "the hash-grid kernels) over 1 GiB, HIP events, 5 repetitions; torch copy_ beside it"}
+            del src, dst
+            if traffic is not None:
+                measured["operator_traffic_over_time_GBps"] = traffic / (dom[1] * 1e-3) / 1e9
+            # What actually binds the two operators on this access pattern: next to the contract's HBM
+            # fraction (algorithmic bytes / 8 TB/s), the floor each operator has on the resource that limits it, and how close
+            # the measured time is to that floor.
+            #  forward: a hashed level's x-pair of corners is one 128-byte line; with uniformly random samples every pair of a
+            #   level finer than the batch's density is its own line, and a CU's L2 -> L1 path moves 64 B/clk: 2 clk per line
+            #   (measured: 38 TCP->TCC requests and 81 TA-busy cycles per gather instruction, profiles/r02_fwd_counters.md).
+            #  backward: the traffic its kernels move (PMC counters, profiles/rNN_pmc_traffic.json; without them: algorithmic
+            #   bytes x the 1.93 measured in round 2) at the copy rate this chip sustains in the same run.
+            n_fine = sum(1 for r in res if float(r) ** dim > 4.0 * n_local) if dim == 3 else 0
+            lines = n_fine * n_local * (2 ** (dim - 1))
+            cus, clk_ghz = 256, 2.4
+            fwd_floor_ms = lines * 2.0 / (cus * clk_ghz * 1e9) * 1e3
+            bwd_traffic = traffic_bwd
+            bwd_bytes = bwd_traffic if bwd_traffic is not None else 1.93 * b_bwd * n_local
+            bwd_floor_ms = bwd_bytes / (measured["copy_read+write"] * 1e9) * 1e3
+            bound_model = {
+                "forward": {"resource": "L2 -> L1 line path of the CUs: 64 B/clk/CU = 2 clk per 128-byte line, 256 CUs at 2.4 GHz",
+                            "what": (f"{n_fine} levels with more than 4 cells per sample (no two samples share a table line in any order; "
+                                     f"the kernel split is another matter: the rows kernel takes levels up to 32 cells per sample) x "
+                                     f"{n_local} samples x {2 ** (dim - 1)} lines (one per x-pair of corners)"),
+                            "ms": fwd_floor_ms, "operator_ms": ms_fwd,
+                            "frac_of_floor": (fwd_floor_ms / ms_fwd) if ms_fwd > 0 else None},
+                "backward": {"resource": "copy rate measured in this run (shacira_stream_probe, read + write)",
+                             "what": ("PMC traffic of the backward's kernels" if bwd_traffic is not None else
+                                      "algorithmic bytes x 1.93 (round-2 PMC ratio; no counters for these kernel sources)"),
+                             "bytes": bwd_bytes, "GBps": measured["copy_read+write"], "ms": bwd_floor_ms, "operator_ms": ms_bwd,
+                             "frac_of_floor": (bwd_floor_ms / ms_bwd) if ms_bwd > 0 else None},
+            }
         out = {
             "metric": "hash-grid samples/sec fwd+bwd (16 lvl, F=2)",
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": args.workload, "dim": dim, "levels": L, "feature_dim": F, "bitwidth": bw,
+            "config": {"workload": args.workload, "full": args.full, "dim": dim, "levels": L, "feature_dim": F, "bitwidth": bw,
                        "table_rows": T, "samples_per_gpu": n_local, "scaling": args.scaling,
                        "plan_hand_off": ("forward builds the batch's plan every step, backward reads it"
                                          if st_plan_bytes else "none (plain operators)"), "plan_bytes": st_plan_bytes,
@@ -827,7 +865,7 @@ def main():
             "psnr_nerf": psnr_nerf,
             "other_configs_1gpu": secondary,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dim, res, bw, F, first_np, T, min(args.cpu_samples, n_local),
                                                args.cpu_budget_s)
             try:   # a reported extra: whatever goes wrong with the prebuilt reference library must not cost the bench line

@@ -119,3 +119,26 @@ def test_ranks_proof_refuses_a_short_world(monkeypatch):
         bench.ranks_proof(0, 4, torch.device("cpu"))   # ... of four
     assert exc.value.code == 3
     assert bench.ranks_proof(0, 3, torch.device("cpu"))["ranks_seen"] == 3
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_rows(tmp_path, monkeypatch):
+    """--dump-outputs: an output within its budget is written whole, a larger one as the same seeded sample of rows on every
+    run; float32 whatever the input precision."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert sum(bench.DUMP_BUDGET.values()) <= 64e6       # the bound on a dump of the headline workload
+    monkeypatch.setattr(bench, "DUMP_BUDGET", {"features": 64 * 4 * 4, "grad_codebook": 1 << 20})
+    feats = torch.arange(1000 * 4, dtype=torch.float64).reshape(1000, 4)
+    grad = torch.randn(300, 2).half()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"features": feats, "grad_codebook": grad})
+    fa, fb = np.load(tmp_path / "a" / "features.npy"), np.load(tmp_path / "b" / "features.npy")
+    assert fa.dtype == np.float32 and fa.shape == (64, 4) and np.array_equal(fa, fb)
+    rows = fa[:, 0].astype(np.int64) // 4
+    assert np.all(np.diff(rows) > 0) and np.array_equal(fa, feats.numpy()[rows].astype(np.float32))
+    g = np.load(tmp_path / "a" / "grad_codebook.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, grad.float().numpy())

@@ -9,7 +9,7 @@ python -c "from bench import kernel_source_hash; print(kernel_source_hash())" > 
 STAGES=${STAGES:-"bench checks stats pmc ctr bctr steps mfma"}    # subset to re-run, e.g. STAGES="bench ctr"
 has() { case " $STAGES " in *" $1 "*) return 0;; esac; return 1; }
 if has bench; then
-( time timeout 600 python bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt ) 2> $OUT/bench_wall.txt
+( time timeout 600 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt ) 2> $OUT/bench_wall.txt
 tail -c 600 $OUT/bench_line.json; cat $OUT/bench_wall.txt
 fi
 if has checks; then
