@@ -106,8 +106,7 @@ SHACIRA_API int shacira_hashgrid_debug_corners(int dim, int64_t num_coords, int 
  *                  (the reference's at::zeros_like + atomicAdd), no pre-zeroing needed
  *   workspace      scratch of at least shacira_hashgrid_backward_workspace_bytes(...) bytes (may be NULL if 0)
  *
- * The reference's `require_grad_coords` output is dead code there (computed into a tensor that is never
- * returned, hashgrid_interpolate.cpp:96-97; wisp/ops/grid.py:111 returns None for coords) and is not provided.
+ * The gradient with respect to the coordinates is a separate call: shacira_hashgrid_coords_backward below.
  */
 SHACIRA_API size_t shacira_hashgrid_backward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                  int codebook_bitwidth, const int32_t *resolutions_host,
@@ -180,6 +179,49 @@ SHACIRA_API int shacira_hashgrid_backward_planned(int dim, int64_t num_coords, i
                                                   const int32_t *codebook_first_idx, int64_t table_rows, const float *coords,
                                                   const void *grad_output, int dtype, void *grad_codebook, const void *plan,
                                                   size_t plan_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Coordinate backward (ABI 11, additive): the gradient of the features with respect to the input coordinates. The reference's
+ * `require_grad_coords` branch (hashgrid_interpolate_cuda.cu:223-269) is dead code there (its result is never returned,
+ * hashgrid_interpolate.cpp:84-96) and is not what is computed here. For sample n, level l, axis a, with the forward's own
+ * transform u = (float)(res_l * ((double)c_a * 0.5 + 0.5)), x = clamp(u, 0, hi_l), frac = x - floor(x), the corner values
+ * t[k, f] of compute_corners' level-local rows (the forward's out-of-table masking: such a corner reads as 0 and its row is
+ * never read outside the table) and g = grad_output[n, l*F + f]:
+ *
+ *   grad_coords[n, a] = sum_l s_l,a * sum_f g[n,l,f] * sum_{corner pairs (k0, k1) that differ only in axis a} W_a(k0) * (t[k1,f] - t[k0,f])
+ *   s_l,a  = 0.5 * res_l where 0 <= u <= hi_l (both ends inclusive: torch.clamp's autograd convention), 0 where the clamp
+ *            acts and for NaN coordinates (the forward maps those to hi_l)
+ *   W_a(k) = product of the other axes' weights (frac or 1 - frac, fp32, as in the forward's weights)
+ *
+ * At a cell boundary the derivative is the one-sided value of the cell floor() picks. fp32 arithmetic: fp16 tables and
+ * gradients are widened, fp64 tables and gradients read as fp32 (the forward's Scalar<double>). ONE expression tree, explicit
+ * fmaf (the library is built with -ffp-contract=off), corner k: bit dim-1-a -> axis a:
+ *   D_f[a] = d(k0_0) * W(k0_0), then fmaf(d(k0), W(k0), D) over the pairs of axis a, k0 ascending, d(k0) = t[k1,f] - t[k0,f],
+ *            W a left-to-right product of the other axes' weights in axis order
+ *   S_l[a] = g_0 * D_0[a], then fmaf(g_f, D_f[a], S) for f ascending
+ *   grad[a] = 0, then fmaf(s_l,a, S_l[a], grad[a]) for l ascending
+ * Every kernel variant evaluates exactly this tree: the result for a sample depends on that sample only, so variants, sample
+ * order and planned or plain calls agree bit for bit.
+ *
+ *   codebook        [table_rows, feature_dim] of `dtype` (the table the forward read)
+ *   grad_output     [num_coords, num_lods*feature_dim] of `dtype`
+ *   grad_coords     out, fp32 [num_coords, dim]; overwritten, not accumulated
+ *   plan            NULL, or the buffer the planned forward of the same coordinates filled (the contract of
+ *                   shacira_hashgrid_backward_planned; ignored for shapes whose forward sorts nothing; SHACIRA_EWORKSPACE when
+ *                   plan_bytes is below shacira_hashgrid_plan_bytes). Lets large 3-D batches walk the samples in sorted order.
+ *   workspace       scratch of shacira_hashgrid_coords_backward_workspace_bytes(...) bytes (0 today: may be NULL)
+ * Validation happens before any HIP call, with the codes of shacira_hashgrid_forward; num_coords == 0 returns 0. No host
+ * synchronisation and no allocation: safe to capture into a graph.
+ */
+SHACIRA_API size_t shacira_hashgrid_coords_backward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                                    int codebook_bitwidth, const int32_t *resolutions_host,
+                                                                    int64_t table_rows, int dtype);
+SHACIRA_API int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                 int codebook_bitwidth, const int32_t *resolutions_host,
+                                                 const int32_t *codebook_first_idx, int64_t table_rows, const float *coords,
+                                                 const void *codebook, const void *grad_output, int dtype, float *grad_coords,
+                                                 const void *plan, size_t plan_bytes, void *workspace,
+                                                 size_t workspace_bytes, void *stream);
 
 /*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
@@ -525,6 +567,9 @@ SHACIRA_API int shacira_stream_probe(int kind, const void *src, void *dst, size_
  *   "bwd_selective_zero": 1 (default) = the backward zeroes only the gradient rows its last pass does not overwrite with
  *               plain stores (all rows outside the hashed levels, plus hashed buckets that received 0 or several work
  *               units); 0 = the whole table first. Same result either way.
+ *   "coord_variant": coordinate backward: -1 (default) = lane pairs over the plan's sorted records for 3-D calls that bring a
+ *               plan (F = 2 / 4, fp32 / fp16), one lane per sample otherwise; 0 = one lane per sample; 3 = lane pairs;
+ *               8 = lane pairs over the plan's records (lane pairs when the call has no plan). Same bits either way.
  * (ABI 7 removed "bwd_fuse", "bwd_groups", "bwd_rows", "bwd_direct_side" and forward variants 1, 2, 4, 5, 7 -- code paths
  * that measured slower in rounds 1-2; they are recorded by git hash in profiles/.)
  */

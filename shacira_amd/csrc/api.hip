@@ -38,6 +38,7 @@ static OptionSlot g_slots[] = {
     {"bwd_brick_span", &Options::bwd_brick_span, 0, 64, {0}},
     {"fwd_direct", &Options::fwd_direct, -1, 1, {-1}},
     {"bwd_ext_fork", &Options::bwd_ext_fork, 0, 1, {1}},
+    {"coord_variant", &Options::coord_variant, -1, 8, {-1}},
 };
 static thread_local Options tl_options;
 const Options &opt() { return tl_options; }
@@ -48,6 +49,7 @@ void options_resolve_item12(int value) { tl_options.bwd_item12 = value; }
 static bool option_value_ok(const OptionSlot &sl, int v) {
     if (v < sl.lo || v > sl.hi) return false;
     if (!std::strcmp(sl.name, "fwd_variant")) return v == -1 || v == 0 || v == 3 || v == 6 || v == 8 || v == 9;
+    if (!std::strcmp(sl.name, "coord_variant")) return v == -1 || v == 0 || v == 3 || v == 8;
     if (!std::strcmp(sl.name, "bin_acc_kib")) return v == 0 || v == 64 || v == 128;
     return true;
 }
@@ -234,6 +236,41 @@ int shacira_hashgrid_backward_levels(int dim, int64_t num_coords, int num_lods, 
     return backward_call(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, codebook_first_idx,
                          table_rows, coords, grad_output, dtype, grad_codebook, level_begin, level_end, flags, nullptr, 0,
                          workspace, workspace_bytes, stream);
+}
+
+size_t shacira_hashgrid_coords_backward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                        int codebook_bitwidth, const int32_t *resolutions_host,
+                                                        int64_t table_rows, int dtype) {
+    (void)dim; (void)num_coords; (void)num_lods; (void)feature_dim; (void)codebook_bitwidth; (void)resolutions_host;
+    (void)table_rows; (void)dtype;
+    return 0;   // every variant is a pure gather (the ABI keeps the argument for later variants)
+}
+
+int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
+                                     const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
+                                     const float *coords, const void *codebook, const void *grad_output, int dtype,
+                                     float *grad_coords, const void *plan, size_t plan_bytes, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    options_snapshot();
+    LevelTable lt;
+    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
+    if (rc) return rc;
+    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16 && dtype != SHACIRA_F64) return SHACIRA_EDTYPE;
+    if (num_coords < 0) return SHACIRA_EINVAL;
+    if (num_coords == 0) return 0;
+    if (!codebook_first_idx || !coords || !codebook || !grad_output || !grad_coords) return SHACIRA_EINVAL;
+    const size_t need = shacira_hashgrid_coords_backward_workspace_bytes(dim, num_coords, num_lods, feature_dim,
+                                                                         codebook_bitwidth, resolutions_host, table_rows,
+                                                                         dtype);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    // the plan of a shape whose forward sorts nothing does not exist: such a buffer is ignored (as in backward_call)
+    if (plan != nullptr) {
+        const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
+        if (!sorts) plan = nullptr;
+        else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
+    }
+    return (int)hashgrid_coord_grad_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, grad_output, grad_coords,
+                                             num_coords, (hipStream_t)stream, plan);
 }
 
 static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,

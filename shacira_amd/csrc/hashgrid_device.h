@@ -41,14 +41,25 @@ inline bool level_is_dense(int dim, int32_t res, int32_t cs) {
 }
 
 // .cu:68-75 for one axis. `t` = (double)c * 0.5 + 0.5 is level independent and hoisted by callers.
+__device__ __forceinline__ float axis_scaled(double t, int32_t res) {
+    return (float)((double)res * t);  // fp64 product narrowed to fp32 (implicit in the reference)
+}
+
 __device__ __forceinline__ void axis_transform(double t, int32_t res, float hi, int32_t &pos, float &fr,
                                                float &ifr) {
-    float x = (float)((double)res * t);  // fp64 product narrowed to fp32 (implicit in the reference)
+    float x = axis_scaled(t, res);
     x = fmaxf(0.0f, fminf(hi, x));       // clamp(): max(a, min(b, x)); NaN -> hi like CUDA's fminf
     float fl = floorf(x);
     pos = (int32_t)fl;
     fr = x - fl;
     ifr = 1.0f - fr;  // (float)(1.0 - (double)fr): a correctly rounded fp32 subtraction
+}
+
+// d x / d c of axis_transform (coordinate backward, hashgrid_coord_grad.hip): 0.5 * res where the clamp passes the scaled
+// coordinate through -- both ends inclusive, torch.clamp's autograd convention -- and 0 where it clamps and for NaN
+__device__ __forceinline__ float axis_slope(double t, int32_t res, float hi) {
+    const float u = axis_scaled(t, res);
+    return (u >= 0.0f && u <= hi) ? 0.5f * (float)res : 0.0f;
 }
 
 __device__ __forceinline__ double axis_unit(float c) { return (double)c * 0.5 + 0.5; }
@@ -96,11 +107,11 @@ template <int DIM> struct Corners {
     float w[NC];       // interpolation weight
 };
 
+// f / g: the per-axis fractions and 1 - fractions the weights are made of (the coordinate backward needs them as well)
 template <int DIM>
 __device__ __forceinline__ void compute_corners(const double (&t)[DIM], int32_t res, float hi, bool dense,
-                                                uint32_t mask, Corners<DIM> &c) {
+                                                uint32_t mask, Corners<DIM> &c, float (&f)[DIM], float (&g)[DIM]) {
     int32_t p[DIM];
-    float f[DIM], g[DIM];
 #pragma unroll
     for (int a = 0; a < DIM; ++a) axis_transform(t[a], res, hi, p[a], f[a], g[a]);
     if constexpr (DIM == 3) {
@@ -142,6 +153,13 @@ __device__ __forceinline__ void compute_corners(const double (&t)[DIM], int32_t 
             for (int j = 0; j < 4; ++j) c.row[j] = ((ux + ((j >> 1) & 1)) ^ ((j & 1) ? hy1 : hy0)) & mask;
         }
     }
+}
+
+template <int DIM>
+__device__ __forceinline__ void compute_corners(const double (&t)[DIM], int32_t res, float hi, bool dense,
+                                                uint32_t mask, Corners<DIM> &c) {
+    float f[DIM], g[DIM];
+    compute_corners<DIM>(t, res, hi, dense, mask, c, f, g);
 }
 
 }  // namespace shacira

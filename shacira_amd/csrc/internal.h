@@ -61,6 +61,10 @@ void sample_plan_view(int dim, int64_t n, const void *plan, SortedBatch &out);
 void sample_plan_grid(int dim, int64_t n, SortedBatch &out);   // block grid only (no buffer)
 hipError_t hashgrid_debug_corners(int dim, const LevelTable &lt, const float *coords, int64_t n, int32_t *idx, float *w,
                                   hipStream_t s);
+// hashgrid_coord_grad.hip: grad_coords [n, dim] fp32 (overwritten); `plan`: the batch's plan or NULL
+hipError_t hashgrid_coord_grad_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
+                                        const float *coords, const void *table, const void *grad_out,
+                                        float *grad_coords, int64_t n, hipStream_t s, const void *plan);
 // hashgrid_bwd.hip
 hipError_t zero_fill_async(float *p, int64_t n, hipStream_t s);   // zero fill as a kernel (graph-capture safe)
 size_t hashgrid_backward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n);
@@ -193,6 +197,7 @@ struct Options {
     int bwd_brick_fork = 2;       // where the brick pass runs: 0 last on the caller's stream, 1 / 2 side stream from behind the front / scatter pass
     int bwd_brick_span = 0;       // blocks per brick unit along x (0 = planner)
     int bwd_ext_fork = 1;         // planned calls: the brick pass's fork event rides on the scatter launch (hipExtLaunchKernelGGL)
+    int coord_variant = -1;       // coordinate backward: -1 rule (8 with a plan in 3-D, else 0), 0 lane per sample, 3 lane pairs, 8 sorted pairs
     int fwd_direct = -1;          // level-per-XCD forward writes the output rows itself (no staging): -1 = small batches, 0 / 1
 };
 const Options &opt();             // the calling thread's snapshot

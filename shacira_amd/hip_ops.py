@@ -276,6 +276,41 @@ def hashgrid_backward(dim, coords, grad_output, table_rows, table_dtype, codeboo
     return grad_codebook
 
 
+def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_idx, resolution, codebook_bitwidth,
+                             plan=None):
+    """Gradient of the features with respect to the coordinates: fp32 [N, dim] (include/shacira_hip.h,
+    shacira_hashgrid_coords_backward). ``codebook`` is the table the forward read; ``grad_output`` [N, L*F] is taken in
+    the table's dtype; ``plan``: the buffer the forward of the SAME coordinate batch filled, or None."""
+    _need_gpu(coords, grad_output, codebook, codebook_first_idx)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float for coords")
+    _check_coords(dim, coords)
+    res = tuple(int(r) for r in resolution)
+    N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
+    dt = _dtype_code(codebook)
+    codebook = codebook.contiguous()
+    if grad_output.dtype != codebook.dtype:
+        grad_output = grad_output.to(codebook.dtype)
+    grad_output = grad_output.contiguous()
+    if tuple(grad_output.shape) != (N, len(res) * F):
+        raise RuntimeError(f"grad_output must be [{N}, {len(res) * F}], got {tuple(grad_output.shape)}")
+    grad_coords = torch.empty((N, dim), dtype=torch.float32, device=coords.device)
+    L = _lib.lib()
+    with _on_device(coords.device):
+        nbytes = int(L.shacira_hashgrid_coords_backward_workspace_bytes(dim, N, len(res), F, int(codebook_bitwidth),
+                                                                         _res_array(res), T, dt))
+        ws = _workspace(coords.device, nbytes)
+        if plan is not None:
+            _need_gpu(plan)
+        rc = L.shacira_hashgrid_coords_backward(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
+                                                _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook),
+                                                _ptr(grad_output), dt, _ptr(grad_coords), _ptr(plan),
+                                                0 if plan is None else plan.numel(), _ptr(ws), nbytes,
+                                                _stream(coords))
+    _lib.check(rc, "hashgrid_coords_backward")
+    return grad_coords
+
+
 def hashgrid_debug_corners(dim, coords, resolution, codebook_bitwidth):
     """Test hook: (rows int32 [N, L, 2^dim], weights fp32 [N, L, 2^dim]) exactly as the kernels compute them."""
     _need_gpu(coords)
