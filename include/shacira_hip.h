@@ -224,6 +224,59 @@ SHACIRA_API int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, in
                                                  size_t workspace_bytes, void *stream);
 
 /*
+ * Triplane sampling (ABI 11, additive): TriplanarGrid (reference wisp/models/grids/triplanar_grid.py). LOD l of a call has
+ * three fp32 planes fmx, fmy, fmz, each the module's NCHW parameter [1, F, S_l, S_l], S_l = 2^lods_host[l] + 1, passed as a
+ * HOST array of 3 * num_lods device pointers ordered [3 * l + p] (p = 0 fmx, 1 fmy, 2 fmz; copied into the kernel arguments,
+ * nothing is concatenated). fmx is read at (y, z), fmy at (x, z), fmz at (x, y): the first coordinate indexes the width (last)
+ * axis. Each read is torch's grid_sample(bilinear, align_corners=True, padding_mode='reflection') in fp32, with the index
+ * math of ATen/native/cuda/GridSampler.cuh:
+ *   ix = ((c + 1) / 2) * (S - 1); reflected over [0, S - 1] (fabs, fmodf, flips = (int)floorf(in / span)); clipped to
+ *   [0, S - 1] with fmaxf / fminf (forward: a NaN or +-inf coordinate becomes texel 0, as the device's ::max does); a value
+ *   that is not finite or outside the int range becomes -100 (every corner out of bounds).
+ *   corners nw (x0, y0), ne (x0+1, y0), sw (x0, y0+1), se (x0+1, y0+1), x0 = (int)floorf(ix), bounds checked per corner;
+ *   weights nw = (x0+1 - ix) * (y0+1 - iy), ne = (ix - x0) * (y0+1 - iy), sw = (x0+1 - ix) * (iy - y0), se = (ix - x0) * (iy - y0).
+ *   value = 0, then value += plane[c, y, x] * w for nw, ne, sw, se (in-bounds corners; separate multiply and add).
+ * Output row of a sample: per LOD [x-plane F | y-plane F | z-plane F].
+ *   multiscale_sum = 0 ('cat'): feats [N, num_lods * 3F], LOD-major.
+ *   multiscale_sum = 1 ('sum'): feats [N, 3F], s = value_0, then s = s + value_l for l ascending.
+ * Callers pass only the selected LODs (the module's 0..lod_idx).
+ *
+ * Backward, the derivatives of the same reads with the _set_grad twins of GridSampler.cuh: clip_coordinates_set_grad
+ * gives gradient 0 at both borders (coordinate exactly -1 or +1 after reflection), reflect_coordinates_set_grad flips the
+ * sign on odd reflections, a non-finite coordinate (-> -100) contributes nothing.
+ *   flags & SHACIRA_TRIPLANE_GRAD_PLANES: grad_planes_host (the same layout of device pointers, each [F, S_l, S_l])
+ *       overwritten with sum_n w_k(n) * g[n, l, p, c] at the four corners. The sum is accumulated with float atomics: two
+ *       runs differ in the last bits. planes_host is not read.
+ *   flags & SHACIRA_TRIPLANE_GRAD_COORDS: grad_coords fp32 [N, 3] overwritten (needs planes_host). Per plane, from 0,
+ *       channel by channel, corners nw, ne, sw, se: gix -/+= v * (y-weight) * g, giy -/+= v * (x-weight) * g (the reference
+ *       kernel's signs and order); d/du = mult_u * gix, d/dv = mult_v * giy with mult = (S - 1) / 2 * reflect sign * clip
+ *       gradient; grad = 0, then += those terms for l ascending, planes x, y, z. No atomics: the same bits every run.
+ *   grad_output: [N, 3F] for 'sum' (every LOD receives the same gradient), [N, num_lods * 3F] for 'cat'.
+ *
+ * Bounds: 1 <= num_lods <= SHACIRA_TRIPLANE_MAX_LODS, 0 <= lods_host[l] <= SHACIRA_TRIPLANE_MAX_LOD,
+ * 1 <= feature_dim <= SHACIRA_TRIPLANE_MAX_FDIM, 0 <= num_coords < 2^31, coordinates fp32 [N, 3]. Validation happens before
+ * any HIP call (SHACIRA_EINVAL: shapes, null pointers, flags; SHACIRA_EWORKSPACE: workspace below the query); num_coords == 0
+ * writes no features (the backward still zeroes the plane gradients). No host synchronisation and no allocation: safe to
+ * capture into a graph.
+ */
+#define SHACIRA_TRIPLANE_MAX_LODS 11
+#define SHACIRA_TRIPLANE_MAX_LOD 10
+#define SHACIRA_TRIPLANE_MAX_FDIM 32
+#define SHACIRA_TRIPLANE_GRAD_PLANES 1
+#define SHACIRA_TRIPLANE_GRAD_COORDS 2
+SHACIRA_API size_t shacira_triplane_forward_workspace_bytes(int64_t num_coords, int num_lods, const int32_t *lods_host,
+                                                            int feature_dim, int multiscale_sum);
+SHACIRA_API int shacira_triplane_forward(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim,
+                                         const float *coords, const float *const *planes_host, int multiscale_sum,
+                                         float *feats, void *workspace, size_t workspace_bytes, void *stream);
+SHACIRA_API size_t shacira_triplane_backward_workspace_bytes(int64_t num_coords, int num_lods, const int32_t *lods_host,
+                                                             int feature_dim, int multiscale_sum, int flags);
+SHACIRA_API int shacira_triplane_backward(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim,
+                                          const float *coords, const float *const *planes_host, const float *grad_output,
+                                          int multiscale_sum, int flags, float *const *grad_planes_host,
+                                          float *grad_coords, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)
@@ -570,6 +623,8 @@ SHACIRA_API int shacira_stream_probe(int kind, const void *src, void *dst, size_
  *   "coord_variant": coordinate backward: -1 (default) = lane pairs over the plan's sorted records for 3-D calls that bring a
  *               plan (F = 2 / 4, fp32 / fp16), one lane per sample otherwise; 0 = one lane per sample; 3 = lane pairs;
  *               8 = lane pairs over the plan's records (lane pairs when the call has no plan). Same bits either way.
+ *   "triplane_layout": triplane forward: -1 (default) = the measured rule, 0 = gathers from the NCHW parameters, 1 = one
+ *               transpose into an HWC copy in the workspace first (profiles/triplane.md). Same bits either way.
  * (ABI 7 removed "bwd_fuse", "bwd_groups", "bwd_rows", "bwd_direct_side" and forward variants 1, 2, 4, 5, 7 -- code paths
  * that measured slower in rounds 1-2; they are recorded by git hash in profiles/.)
  */

@@ -39,6 +39,7 @@ static OptionSlot g_slots[] = {
     {"fwd_direct", &Options::fwd_direct, -1, 1, {-1}},
     {"bwd_ext_fork", &Options::bwd_ext_fork, 0, 1, {1}},
     {"coord_variant", &Options::coord_variant, -1, 8, {-1}},
+    {"triplane_layout", &Options::triplane_layout, -1, 1, {-1}},
 };
 static thread_local Options tl_options;
 const Options &opt() { return tl_options; }
@@ -271,6 +272,88 @@ int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, int num_lods, 
     }
     return (int)hashgrid_coord_grad_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, grad_output, grad_coords,
                                              num_coords, (hipStream_t)stream, plan);
+}
+
+// ---- triplanes ---------------------------------------------------------------------------------------------------------
+static int triplane_args(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim, TriplaneArgs &a) {
+    if (num_coords < 0 || num_coords > (int64_t)INT32_MAX) return SHACIRA_EINVAL;
+    if (num_lods < 1 || num_lods > SHACIRA_TRIPLANE_MAX_LODS || !lods_host) return SHACIRA_EINVAL;
+    if (feature_dim < 1 || feature_dim > SHACIRA_TRIPLANE_MAX_FDIM) return SHACIRA_EINVAL;
+    std::memset(&a, 0, sizeof(a));
+    a.num_lods = num_lods;
+    a.fdim = feature_dim;
+    for (int l = 0; l < num_lods; ++l) {
+        if (lods_host[l] < 0 || lods_host[l] > SHACIRA_TRIPLANE_MAX_LOD) return SHACIRA_EINVAL;
+        a.side[l] = (1 << lods_host[l]) + 1;
+    }
+    return 0;
+}
+
+static int triplane_pointers(int num_lods, const float *const *host, TriplaneArgs &a, bool grad) {
+    if (!host) return SHACIRA_EINVAL;
+    for (int q = 0; q < 3 * num_lods; ++q) {
+        if (!host[q]) return SHACIRA_EINVAL;
+        if (grad) a.grad[q] = const_cast<float *>(host[q]);
+        else a.plane[q] = host[q];
+    }
+    return 0;
+}
+
+size_t shacira_triplane_forward_workspace_bytes(int64_t num_coords, int num_lods, const int32_t *lods_host,
+                                                int feature_dim, int multiscale_sum) {
+    options_snapshot();
+    TriplaneArgs a;
+    if (triplane_args(num_coords, num_lods, lods_host, feature_dim, a)) return 0;
+    return triplane_forward_workspace(a, num_coords);
+}
+
+int shacira_triplane_forward(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim,
+                             const float *coords, const float *const *planes_host, int multiscale_sum, float *feats,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+    options_snapshot();
+    TriplaneArgs a;
+    if (int rc = triplane_args(num_coords, num_lods, lods_host, feature_dim, a)) return rc;
+    if (multiscale_sum != 0 && multiscale_sum != 1) return SHACIRA_EINVAL;
+    if (num_coords == 0) return 0;
+    if (!coords || !feats) return SHACIRA_EINVAL;
+    if (int rc = triplane_pointers(num_lods, planes_host, a, false)) return rc;
+    const size_t need = triplane_forward_workspace(a, num_coords);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    return (int)triplane_forward_dispatch(a, coords, multiscale_sum, feats, workspace, num_coords, (hipStream_t)stream);
+}
+
+size_t shacira_triplane_backward_workspace_bytes(int64_t num_coords, int num_lods, const int32_t *lods_host,
+                                                 int feature_dim, int multiscale_sum, int flags) {
+    TriplaneArgs a;
+    if (triplane_args(num_coords, num_lods, lods_host, feature_dim, a)) return 0;
+    if ((flags & SHACIRA_TRIPLANE_GRAD_PLANES) == 0) return 0;
+    return triplane_backward_workspace(a, multiscale_sum, num_coords);
+}
+
+int shacira_triplane_backward(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim,
+                              const float *coords, const float *const *planes_host, const float *grad_output,
+                              int multiscale_sum, int flags, float *const *grad_planes_host, float *grad_coords,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+    TriplaneArgs a;
+    if (int rc = triplane_args(num_coords, num_lods, lods_host, feature_dim, a)) return rc;
+    if (multiscale_sum != 0 && multiscale_sum != 1) return SHACIRA_EINVAL;
+    if (flags <= 0 || (flags & ~(SHACIRA_TRIPLANE_GRAD_PLANES | SHACIRA_TRIPLANE_GRAD_COORDS)) != 0) return SHACIRA_EINVAL;
+    const bool planes = (flags & SHACIRA_TRIPLANE_GRAD_PLANES) != 0;
+    const bool want_coords = (flags & SHACIRA_TRIPLANE_GRAD_COORDS) != 0;
+    if (planes)
+        if (int rc = triplane_pointers(num_lods, const_cast<const float *const *>(grad_planes_host), a, true)) return rc;
+    if (num_coords > 0) {
+        if (!coords || !grad_output) return SHACIRA_EINVAL;
+        if (want_coords) {
+            if (!grad_coords) return SHACIRA_EINVAL;
+            if (int rc = triplane_pointers(num_lods, planes_host, a, false)) return rc;
+        }
+    }
+    const size_t need = planes ? triplane_backward_workspace(a, multiscale_sum, num_coords) : 0;
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    return (int)triplane_backward_dispatch(a, coords, grad_output, multiscale_sum, planes,
+                                           want_coords ? grad_coords : nullptr, workspace, num_coords,
+                                           (hipStream_t)stream);
 }
 
 static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,

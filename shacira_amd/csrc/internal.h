@@ -74,6 +74,33 @@ hipError_t hashgrid_backward_dispatch(int dim, int dtype, const LevelTable &lt, 
                                       const float *coords, const void *grad_out, void *grad_table, void *workspace,
                                       size_t workspace_bytes, int64_t n, hipStream_t s, const void *plan = nullptr);
 
+// triplane.hip: the planes of one call, by value in the kernel arguments ([3 * l + p], p = 0 fmx, 1 fmy, 2 fmz)
+struct TriplaneArgs {
+    const float *plane[3 * SHACIRA_TRIPLANE_MAX_LODS];   // NCHW [fdim, side, side] each
+    float *grad[3 * SHACIRA_TRIPLANE_MAX_LODS];          // backward: the same shapes (overwritten)
+    int64_t hwc_off[3 * SHACIRA_TRIPLANE_MAX_LODS];      // forward, HWC layout: plane offsets in the workspace (floats)
+    int32_t side[SHACIRA_TRIPLANE_MAX_LODS];             // 2^lod + 1 texels
+    int32_t num_lods;
+    int32_t fdim;
+};
+// the plane backward's sort and windows (a function of the shape, built on the host)
+struct TriBwdPlan {
+    int32_t nb, nbins;        // blocks per cube axis, nb^3
+    int32_t sort_side;        // texels a side of the finest LOD (the sort's coordinate frame)
+    int32_t cells;            // its cells per block edge
+    int32_t sum;              // grad_output is [N, 3F] ('sum') or [N, L * 3F]
+    int32_t win[SHACIRA_TRIPLANE_MAX_LODS];   // window side per LOD in texels, 0 = no LDS window (global adds)
+};
+constexpr int kTriDefaultHwc = 1;   // forward layout rule (option triplane_layout = -1), profiles/triplane.md
+size_t triplane_forward_workspace(const TriplaneArgs &a, int64_t n);
+hipError_t triplane_forward_dispatch(TriplaneArgs a, const float *coords, int sum, float *feats, void *workspace,
+                                     int64_t n, hipStream_t s);
+void triplane_backward_plan(const TriplaneArgs &a, int sum, TriBwdPlan &bp);
+size_t triplane_backward_workspace(const TriplaneArgs &a, int sum, int64_t n);
+// planes: write the plane gradients; grad_coords != NULL: the coordinate gradient (reads a.plane)
+hipError_t triplane_backward_dispatch(const TriplaneArgs &a, const float *coords, const float *grad_out, int sum,
+                                      bool planes, float *grad_coords, void *workspace, int64_t n, hipStream_t s);
+
 // latent.hip
 struct DecodeArgs {
     const float *latent, *div, *matrix, *colscale, *shift;
@@ -199,6 +226,7 @@ struct Options {
     int bwd_ext_fork = 1;         // planned calls: the brick pass's fork event rides on the scatter launch (hipExtLaunchKernelGGL)
     int coord_variant = -1;       // coordinate backward: -1 rule (8 with a plan in 3-D, else 0), 0 lane per sample, 3 lane pairs, 8 sorted pairs
     int fwd_direct = -1;          // level-per-XCD forward writes the output rows itself (no staging): -1 = small batches, 0 / 1
+    int triplane_layout = -1;     // triplane forward reads: -1 rule (kTriDefaultHwc), 0 the NCHW parameters, 1 an HWC copy
 };
 const Options &opt();             // the calling thread's snapshot
 void options_snapshot();          // taken at every extern "C" entry point that reads options

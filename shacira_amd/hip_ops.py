@@ -708,3 +708,95 @@ def latent_symbol_counts(latent):
         _lib.check(L.shacira_latent_symbol_histogram(rows, ld, _ptr(latent), _ptr(minmax), nbins, _ptr(counts),
                                                      _stream(latent)), "shacira_latent_symbol_histogram")
     return mm[:, 0].long(), counts
+
+
+# ---- triplanes (include/shacira_hip.h, shacira_triplane_*) -----------------------------------------------------------------
+def _plane_array(planes):
+    return (ctypes.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+
+
+def _triplane_shape(coords, lods, planes):
+    _need_gpu(coords, *planes)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float for coords")
+    _check_coords(3, coords)
+    lods = tuple(int(l) for l in lods)
+    if len(planes) != 3 * len(lods):
+        raise RuntimeError(f"shacira_amd: {len(lods)} LODs need {3 * len(lods)} planes, got {len(planes)}")
+    fdim = planes[0].shape[1] if planes[0].dim() == 4 else -1
+    for l, lod in enumerate(lods):
+        side = (1 << lod) + 1 if lod >= 0 else 0
+        for p in planes[3 * l:3 * l + 3]:
+            if (p.dtype != torch.float32 or tuple(p.shape) != (1, fdim, side, side) or not p.is_contiguous()
+                    or p.device != coords.device):
+                raise RuntimeError(f"shacira_amd: LOD {l} planes must be contiguous fp32 [1, {fdim}, {side}, {side}] on "
+                                   f"{coords.device}, got {p.dtype} {tuple(p.shape)}")
+    return lods, fdim
+
+
+def triplane_forward(coords, lods, planes, multiscale_sum):
+    """Features of the triplanes at ``coords`` [N, 3] fp32: [N, 3F] (``multiscale_sum``) or [N, len(lods) * 3F].
+
+    ``planes``: the 3 * len(lods) NCHW plane parameters [1, F, 2^lod + 1, 2^lod + 1], ordered fmx, fmy, fmz per LOD."""
+    lods, fdim = _triplane_shape(coords, lods, planes)
+    N = coords.shape[0]
+    K = 3 * fdim if multiscale_sum else 3 * fdim * len(lods)
+    feats = torch.empty((N, K), dtype=torch.float32, device=coords.device)
+    L = _lib.lib()
+    la = _res_array(lods)
+    with _on_device(coords.device):
+        nbytes = int(L.shacira_triplane_forward_workspace_bytes(N, len(lods), la, fdim, int(bool(multiscale_sum))))
+        ws = _workspace(coords.device, nbytes)
+        rc = L.shacira_triplane_forward(N, len(lods), la, fdim, _ptr(coords), _plane_array(planes),
+                                        int(bool(multiscale_sum)), _ptr(feats), _ptr(ws), nbytes, _stream(coords))
+    _lib.check(rc, "triplane_forward")
+    return feats
+
+
+def triplane_backward(coords, lods, feature_dim, grad_output, multiscale_sum, planes=None, need_planes=True,
+                      need_coords=False):
+    """(plane gradients: one fp32 [1, F, S, S] tensor per plane, or None; coordinate gradient fp32 [N, 3], or None).
+
+    ``planes`` (the forward's planes) are needed, and their values read, only when ``need_coords``. The plane gradients
+    come from float atomics: two runs differ in the last bits."""
+    lods = tuple(int(l) for l in lods)
+    fdim = int(feature_dim)
+    if need_coords:
+        lods, fdim = _triplane_shape(coords, lods, planes)
+    else:
+        _need_gpu(coords)
+        if coords.dtype != torch.float32:
+            raise RuntimeError("expected scalar type Float for coords")
+        _check_coords(3, coords)
+        if min(lods, default=-1) < 0:
+            raise RuntimeError("shacira_amd: triplane LODs must be >= 0")
+    N = coords.shape[0]
+    K = 3 * fdim if multiscale_sum else 3 * fdim * len(lods)
+    if grad_output.dtype != torch.float32:
+        grad_output = grad_output.float()
+    grad_output = grad_output.contiguous()
+    _need_gpu(grad_output)
+    if tuple(grad_output.shape) != (N, K):
+        raise RuntimeError(f"grad_output must be [{N}, {K}], got {tuple(grad_output.shape)}")
+    flags = (_lib.TRIPLANE_GRAD_PLANES if need_planes else 0) | (_lib.TRIPLANE_GRAD_COORDS if need_coords else 0)
+    if not flags:
+        return None, None
+    dev = coords.device
+    grads = None
+    if need_planes:
+        grads = [torch.empty((1, fdim, (1 << lod) + 1, (1 << lod) + 1), dtype=torch.float32, device=dev)
+                 for lod in lods for _ in range(3)]
+    grad_coords = torch.empty((N, 3), dtype=torch.float32, device=dev) if need_coords else None
+    L = _lib.lib()
+    la = _res_array(lods)
+    with _on_device(dev):
+        nbytes = int(L.shacira_triplane_backward_workspace_bytes(N, len(lods), la, fdim, int(bool(multiscale_sum)),
+                                                                 flags))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_triplane_backward(N, len(lods), la, fdim, _ptr(coords),
+                                         _plane_array(planes) if need_coords else None, _ptr(grad_output),
+                                         int(bool(multiscale_sum)), flags,
+                                         _plane_array(grads) if grads is not None else None, _ptr(grad_coords),
+                                         _ptr(ws), nbytes, _stream(coords))
+    _lib.check(rc, "triplane_backward")
+    return grads, grad_coords

@@ -162,3 +162,6 @@ class OctreeAS(BaseAS):
         if level != self.max_level:
             raise NotImplementedError("only the dense BLAS level is materialised")
         return self.points
+
+
+from .aabb_as import AxisAlignedBBoxAS  # noqa: E402  (subclasses OctreeAS above)
