@@ -277,6 +277,67 @@ SHACIRA_API int shacira_triplane_backward(int64_t num_coords, int num_lods, cons
                                           float *grad_coords, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Octree feature lookup (ABI 11, additive): OctreeGrid / CodebookOctreeGrid (reference wisp/models/grids/octree_grid.py,
+ * kaolin's unbatched_interpolate_trilinear plus the per-level glue of octree_grid.py:303-391). Level l of a call has
+ *   levels_host[l]         its octree level v: G = 2^v cells and S = G + 1 lattice points per axis;
+ *   tables_host[l]         fp32 [C + 1, F] row-major, C = rows_host[l] corner rows plus the reference's padding row (never
+ *                          read; its gradient is zero);
+ *   occupancy_host[l]      uint32 [ceil(G^3 / 32)]: bit (key & 31) of word (key >> 5), key = (x * G + y) * G + z, is set
+ *                          where cell (x, y, z) is occupied;
+ *   corner_index_host[l]   uint32 [ceil(S^3 / 32)][2]: per 32 lattice keys, key = (x * S + y) * S + z, {bits, rows before}:
+ *                          a set bit marks a lattice point that is a corner of an occupied cell, and its table row is
+ *                          rows before + popcount(bits below it). The rows are the corners in ascending key; the two z
+ *                          corners of a cell edge are therefore rows r and r + 1.
+ * All four are HOST arrays of num_levels entries (device pointers copied into the kernel arguments).
+ *   Cell location, fp32: p = (x + 1) * (G / 2) (only the addition rounds), cell = floor(p), t = p - cell.
+ *   A level contributes zeros where a component of p is not in [0, G) (a NaN or +-inf coordinate included) or the cell is
+ *   unoccupied (or the index disagrees with rows_host: a row outside [0, C)). Otherwise value = sum_k w_k * row(corner k),
+ *   k = 0..7 ascending, corner k = cell + (k >> 2 & 1, k >> 1 & 1, k & 1), w_k = wx * wy * wz with t or 1 - t per axis
+ *   (separate multiplies and adds).
+ *   multiscale_sum = 0 ('cat'): feats [N, num_levels * F], levels in the order given.
+ *   multiscale_sum = 1 ('sum'): feats [N, F], s = value_0, then s = s + value_l for l ascending.
+ * One launch over the samples serves every level and writes the final layout.
+ *
+ * Backward:
+ *   flags & SHACIRA_OCTREE_GRAD_FEATURES: grad_tables_host[l] fp32 [C + 1, F] is OVERWRITTEN (zeroed by the call, padding
+ *       row included) with sum_n w_k(n) * g[n, l, :] at the eight corner rows. tables_host is not read. The samples are
+ *       counting-sorted by a block of cells of the finest level; a workgroup sums a block's contributions per level in LDS
+ *       windows and flushes the non-zero entries with global float adds, so two runs differ in the last bits. The result
+ *       does not depend on the order of the batch beyond that.
+ *   flags & SHACIRA_OCTREE_GRAD_COORDS: grad_coords fp32 [N, 3] overwritten (reads tables_host):
+ *       d/dx = sum_l (G_l / 2) * sum_k (dw_k / dt_x) * <row_k, g_l>, zero where the level contributes zero. A gather, one
+ *       lane per sample, no atomics: the same bits every run. First order only.
+ *   grad_output: [N, F] for 'sum' (every level receives the same gradient), [N, num_levels * F] for 'cat'.
+ *
+ * Bounds: 1 <= num_levels <= SHACIRA_OCTREE_MAX_LEVELS, 0 <= levels_host[l] <= SHACIRA_OCTREE_MAX_LEVEL,
+ * 1 <= feature_dim <= SHACIRA_OCTREE_MAX_FDIM (compile-time variants for F = 1, 2, 4, 5, 8, 16; F = 5 and F = 4 are the
+ * tuned cases), 0 <= rows_host[l] <= S^3, 0 <= num_coords < 2^31, coordinates fp32 [N, 3]. Validation happens before any HIP
+ * call (SHACIRA_EINVAL: shapes, null pointers, flags; SHACIRA_EWORKSPACE: workspace below the query). No coordinate value
+ * causes an out-of-bounds read; num_coords == 0 writes no features (the backward still zeroes the table gradients). No host
+ * synchronisation and no allocation: stream-ordered and safe to capture into a graph.
+ */
+#define SHACIRA_OCTREE_MAX_LEVELS 11
+#define SHACIRA_OCTREE_MAX_LEVEL 10
+#define SHACIRA_OCTREE_MAX_FDIM 32
+#define SHACIRA_OCTREE_GRAD_FEATURES 1
+#define SHACIRA_OCTREE_GRAD_COORDS 2
+SHACIRA_API size_t shacira_octree_forward_workspace_bytes(int64_t num_coords, int num_levels, const int32_t *levels_host,
+                                                          int feature_dim, int multiscale_sum);
+SHACIRA_API int shacira_octree_forward(int64_t num_coords, int num_levels, const int32_t *levels_host, int feature_dim,
+                                       const float *coords, const float *const *tables_host, const int64_t *rows_host,
+                                       const void *const *corner_index_host, const void *const *occupancy_host,
+                                       int multiscale_sum, float *feats, void *workspace, size_t workspace_bytes,
+                                       void *stream);
+SHACIRA_API size_t shacira_octree_backward_workspace_bytes(int64_t num_coords, int num_levels, const int32_t *levels_host,
+                                                           int feature_dim, int multiscale_sum, int flags);
+SHACIRA_API int shacira_octree_backward(int64_t num_coords, int num_levels, const int32_t *levels_host, int feature_dim,
+                                        const float *coords, const float *const *tables_host, const int64_t *rows_host,
+                                        const void *const *corner_index_host, const void *const *occupancy_host,
+                                        const float *grad_output, int multiscale_sum, int flags,
+                                        float *const *grad_tables_host, float *grad_coords, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

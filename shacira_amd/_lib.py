@@ -16,6 +16,7 @@ EINVAL, EDTYPE, EODD, EWORKSPACE = -1, -2, -3, -4
 BWD_STAGE_ALL_LEVELS, BWD_REUSE_STAGED = 1, 2
 PLAN_READY = 1
 TRIPLANE_GRAD_PLANES, TRIPLANE_GRAD_COORDS = 1, 2
+OCTREE_GRAD_FEATURES, OCTREE_GRAD_COORDS = 1, 2
 
 _lock = threading.Lock()
 _lib = None
@@ -47,6 +48,10 @@ SIGNATURES = {
     "shacira_triplane_forward": (_i, [_i64, _i, _p, _i, _p, _p, _i, _p, _p, _sz, _p]),
     "shacira_triplane_backward_workspace_bytes": (_sz, [_i64, _i, _p, _i, _i, _i]),
     "shacira_triplane_backward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "shacira_octree_forward_workspace_bytes": (_sz, [_i64, _i, _p, _i, _i]),
+    "shacira_octree_forward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p]),
+    "shacira_octree_backward_workspace_bytes": (_sz, [_i64, _i, _p, _i, _i, _i]),
+    "shacira_octree_backward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "shacira_latent_decode_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),
     "shacira_latent_decode_backward_workspace_bytes": (_sz, [_i64, _i, _i]),
     "shacira_latent_decode_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -356,6 +356,111 @@ int shacira_triplane_backward(int64_t num_coords, int num_lods, const int32_t *l
                                            (hipStream_t)stream);
 }
 
+// ---- octree grids --------------------------------------------------------------------------------------------------------
+static int octree_args(int64_t num_coords, int num_levels, const int32_t *levels_host, int feature_dim, OctreeArgs &a) {
+    if (num_coords < 0 || num_coords > (int64_t)INT32_MAX) return SHACIRA_EINVAL;
+    if (num_levels < 1 || num_levels > SHACIRA_OCTREE_MAX_LEVELS || !levels_host) return SHACIRA_EINVAL;
+    if (feature_dim < 1 || feature_dim > SHACIRA_OCTREE_MAX_FDIM) return SHACIRA_EINVAL;
+    std::memset(&a, 0, sizeof(a));
+    a.num_levels = num_levels;
+    a.fdim = feature_dim;
+    for (int l = 0; l < num_levels; ++l) {
+        if (levels_host[l] < 0 || levels_host[l] > SHACIRA_OCTREE_MAX_LEVEL) return SHACIRA_EINVAL;
+        a.level[l] = levels_host[l];
+    }
+    return 0;
+}
+
+static int octree_rows(const int64_t *rows_host, OctreeArgs &a) {
+    if (!rows_host) return SHACIRA_EINVAL;
+    for (int l = 0; l < a.num_levels; ++l) {
+        const int64_t side = ((int64_t)1 << a.level[l]) + 1;
+        if (rows_host[l] < 0 || rows_host[l] > side * side * side) return SHACIRA_EINVAL;
+        a.rows[l] = rows_host[l];
+    }
+    return 0;
+}
+
+static int octree_index(const void *const *corner_index_host, const void *const *occupancy_host, OctreeArgs &a) {
+    if (!corner_index_host || !occupancy_host) return SHACIRA_EINVAL;
+    for (int l = 0; l < a.num_levels; ++l) {
+        if (!corner_index_host[l] || !occupancy_host[l]) return SHACIRA_EINVAL;
+        a.corner[l] = static_cast<const uint2 *>(corner_index_host[l]);
+        a.occ[l] = static_cast<const uint32_t *>(occupancy_host[l]);
+    }
+    return 0;
+}
+
+static int octree_tables(const float *const *tables_host, OctreeArgs &a) {
+    if (!tables_host) return SHACIRA_EINVAL;
+    for (int l = 0; l < a.num_levels; ++l) {
+        if (!tables_host[l]) return SHACIRA_EINVAL;
+        a.table[l] = tables_host[l];
+    }
+    return 0;
+}
+
+size_t shacira_octree_forward_workspace_bytes(int64_t num_coords, int num_levels, const int32_t *levels_host,
+                                              int feature_dim, int multiscale_sum) {
+    return 0;   // the forward needs none; the query keeps the calling sequence of the other operators
+}
+
+int shacira_octree_forward(int64_t num_coords, int num_levels, const int32_t *levels_host, int feature_dim,
+                           const float *coords, const float *const *tables_host, const int64_t *rows_host,
+                           const void *const *corner_index_host, const void *const *occupancy_host, int multiscale_sum,
+                           float *feats, void *workspace, size_t workspace_bytes, void *stream) {
+    OctreeArgs a;
+    if (int rc = octree_args(num_coords, num_levels, levels_host, feature_dim, a)) return rc;
+    if (multiscale_sum != 0 && multiscale_sum != 1) return SHACIRA_EINVAL;
+    if (int rc = octree_rows(rows_host, a)) return rc;
+    if (num_coords == 0) return 0;
+    if (!coords || !feats) return SHACIRA_EINVAL;
+    if (int rc = octree_tables(tables_host, a)) return rc;
+    if (int rc = octree_index(corner_index_host, occupancy_host, a)) return rc;
+    return (int)octree_forward_dispatch(a, coords, multiscale_sum, feats, num_coords, (hipStream_t)stream);
+}
+
+size_t shacira_octree_backward_workspace_bytes(int64_t num_coords, int num_levels, const int32_t *levels_host,
+                                               int feature_dim, int multiscale_sum, int flags) {
+    OctreeArgs a;
+    if (octree_args(num_coords, num_levels, levels_host, feature_dim, a)) return 0;
+    if ((flags & SHACIRA_OCTREE_GRAD_FEATURES) == 0) return 0;
+    return octree_backward_workspace(a, multiscale_sum, num_coords);
+}
+
+int shacira_octree_backward(int64_t num_coords, int num_levels, const int32_t *levels_host, int feature_dim,
+                            const float *coords, const float *const *tables_host, const int64_t *rows_host,
+                            const void *const *corner_index_host, const void *const *occupancy_host,
+                            const float *grad_output, int multiscale_sum, int flags, float *const *grad_tables_host,
+                            float *grad_coords, void *workspace, size_t workspace_bytes, void *stream) {
+    OctreeArgs a;
+    if (int rc = octree_args(num_coords, num_levels, levels_host, feature_dim, a)) return rc;
+    if (multiscale_sum != 0 && multiscale_sum != 1) return SHACIRA_EINVAL;
+    if (flags <= 0 || (flags & ~(SHACIRA_OCTREE_GRAD_FEATURES | SHACIRA_OCTREE_GRAD_COORDS)) != 0) return SHACIRA_EINVAL;
+    if (int rc = octree_rows(rows_host, a)) return rc;
+    const bool features = (flags & SHACIRA_OCTREE_GRAD_FEATURES) != 0;
+    const bool want_coords = (flags & SHACIRA_OCTREE_GRAD_COORDS) != 0;
+    if (features) {
+        if (!grad_tables_host) return SHACIRA_EINVAL;
+        for (int l = 0; l < num_levels; ++l) {
+            if (!grad_tables_host[l]) return SHACIRA_EINVAL;
+            a.grad[l] = grad_tables_host[l];
+        }
+    }
+    if (num_coords > 0) {
+        if (!coords || !grad_output) return SHACIRA_EINVAL;
+        if (int rc = octree_index(corner_index_host, occupancy_host, a)) return rc;
+        if (want_coords) {
+            if (!grad_coords) return SHACIRA_EINVAL;
+            if (int rc = octree_tables(tables_host, a)) return rc;
+        }
+    }
+    const size_t need = features ? octree_backward_workspace(a, multiscale_sum, num_coords) : 0;
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    return (int)octree_backward_dispatch(a, coords, grad_output, multiscale_sum, features,
+                                         want_coords ? grad_coords : nullptr, workspace, num_coords, (hipStream_t)stream);
+}
+
 static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
                          const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
                          const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,

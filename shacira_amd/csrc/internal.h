@@ -101,6 +101,35 @@ size_t triplane_backward_workspace(const TriplaneArgs &a, int sum, int64_t n);
 hipError_t triplane_backward_dispatch(const TriplaneArgs &a, const float *coords, const float *grad_out, int sum,
                                       bool planes, float *grad_coords, void *workspace, int64_t n, hipStream_t s);
 
+// octree.hip: the levels of one call, by value in the kernel arguments
+struct OctreeArgs {
+    const float *table[SHACIRA_OCTREE_MAX_LEVELS];      // [rows + 1, fdim]
+    float *grad[SHACIRA_OCTREE_MAX_LEVELS];             // backward: the same shapes (overwritten)
+    const uint2 *corner[SHACIRA_OCTREE_MAX_LEVELS];     // per 32 lattice keys {bits, rows before}
+    const uint32_t *occ[SHACIRA_OCTREE_MAX_LEVELS];     // cell bits
+    int64_t rows[SHACIRA_OCTREE_MAX_LEVELS];            // corner rows C (the padding row not counted)
+    int32_t level[SHACIRA_OCTREE_MAX_LEVELS];
+    int32_t num_levels;
+    int32_t fdim;
+};
+// the feature backward's sort and LDS windows (a function of the shape, built on the host)
+struct OctBwdPlan {
+    int32_t fine;             // the finest level of the call (the sort's cell frame)
+    int32_t cells_log2;       // log2 of a block's edge in cells of that level
+    int32_t nb, nbins;        // blocks per axis, nb^3
+    int32_t sum;              // grad_output is [N, F] ('sum') or [N, L * F]
+    int32_t wside[SHACIRA_OCTREE_MAX_LEVELS];   // window side per level in lattice points, 0 = no window (global adds)
+    int32_t woff[SHACIRA_OCTREE_MAX_LEVELS];    // its offset in LDS (floats)
+    int32_t wtotal;           // floats of LDS
+};
+void octree_backward_plan(const OctreeArgs &a, int sum, OctBwdPlan &bp);
+size_t octree_backward_workspace(const OctreeArgs &a, int sum, int64_t n);
+hipError_t octree_forward_dispatch(const OctreeArgs &a, const float *coords, int sum, float *feats, int64_t n,
+                                   hipStream_t s);
+// features: write the table gradients; grad_coords != NULL: the coordinate gradient (reads a.table)
+hipError_t octree_backward_dispatch(const OctreeArgs &a, const float *coords, const float *grad_out, int sum,
+                                    bool features, float *grad_coords, void *workspace, int64_t n, hipStream_t s);
+
 // latent.hip
 struct DecodeArgs {
     const float *latent, *div, *matrix, *colscale, *shift;

@@ -618,6 +618,7 @@ class GraphedNerfFitter:
         new = self.nef.grid.blas
         if new is not self.blas:
             self.blas.occupancy_grid.copy_(new.occupancy_grid.to(self.device))
+            self.blas.occupancy_changed()      # written in place: the coarser levels cached from it are stale
             self.blas.points, self.blas.pyramid = new.points, new.pyramid
             self.nef.grid.blas = self.blas
         self.prepare()

@@ -800,3 +800,98 @@ def triplane_backward(coords, lods, feature_dim, grad_output, multiscale_sum, pl
                                          _ptr(ws), nbytes, _stream(coords))
     _lib.check(rc, "triplane_backward")
     return grads, grad_coords
+
+
+# ---- octree grids (include/shacira_hip.h, shacira_octree_*) ----------------------------------------------------------------
+def _octree_shape(coords, levels, tables, fdim=None):
+    """``levels``: one ``wisp.ops.octree.OctreeLevelIndex`` per level, on the coordinates' device."""
+    _need_gpu(coords)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float for coords")
+    _check_coords(3, coords)
+    if not levels:
+        raise RuntimeError("shacira_amd: the octree lookup needs at least one level")
+    if tables is not None:
+        _need_gpu(*tables)
+        if len(tables) != len(levels):
+            raise RuntimeError(f"shacira_amd: {len(levels)} levels need {len(levels)} tables, got {len(tables)}")
+        fdim = tables[0].shape[1] if tables[0].dim() == 2 else -1
+    for l, li in enumerate(levels):
+        G = 1 << li.level
+        S = G + 1
+        want_ci, want_occ = ((S ** 3 + 31) // 32, 2), ((G ** 3 + 31) // 32,)
+        for name, t, want in (("corner index", li.corner_index, want_ci), ("occupancy", li.occupancy, want_occ)):
+            if (t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous() or t.device != coords.device):
+                raise RuntimeError(f"shacira_amd: level {li.level} {name} must be contiguous int32 {want} on "
+                                   f"{coords.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if tables is not None:
+            t = tables[l]
+            if (t.dtype != torch.float32 or tuple(t.shape) != (li.rows + 1, fdim) or not t.is_contiguous()
+                    or t.device != coords.device):
+                raise RuntimeError(f"shacira_amd: level {li.level} table must be contiguous fp32 [{li.rows + 1}, {fdim}] on "
+                                   f"{coords.device}, got {t.dtype} {tuple(t.shape)}")
+    return int(fdim)
+
+
+def _octree_arrays(levels):
+    n = len(levels)
+    return (_res_array(tuple(li.level for li in levels)), (ctypes.c_int64 * n)(*[li.rows for li in levels]),
+            (ctypes.c_void_p * n)(*[li.corner_index.data_ptr() for li in levels]),
+            (ctypes.c_void_p * n)(*[li.occupancy.data_ptr() for li in levels]))
+
+
+def octree_forward(coords, levels, tables, multiscale_sum):
+    """Trilinear octree features at ``coords`` [N, 3] fp32: [N, F] (``multiscale_sum``) or [N, len(levels) * F].
+
+    ``levels``: the ``OctreeLevelIndex`` of each level; ``tables``: its fp32 feature table [C_l + 1, F]."""
+    fdim = _octree_shape(coords, levels, tables)
+    N = coords.shape[0]
+    K = fdim if multiscale_sum else fdim * len(levels)
+    feats = torch.empty((N, K), dtype=torch.float32, device=coords.device)
+    L = _lib.lib()
+    la, rows, ci, occ = _octree_arrays(levels)
+    with _on_device(coords.device):
+        nbytes = int(L.shacira_octree_forward_workspace_bytes(N, len(levels), la, fdim, int(bool(multiscale_sum))))
+        ws = _workspace(coords.device, nbytes)
+        rc = L.shacira_octree_forward(N, len(levels), la, fdim, _ptr(coords), _plane_array(tables), rows, ci, occ,
+                                      int(bool(multiscale_sum)), _ptr(feats), _ptr(ws), nbytes, _stream(coords))
+    _lib.check(rc, "octree_forward")
+    return feats
+
+
+def octree_backward(coords, levels, feature_dim, grad_output, multiscale_sum, features=None, need_features=True,
+                    need_coords=False):
+    """(table gradients: one fp32 [C_l + 1, F] tensor per level, or None; coordinate gradient fp32 [N, 3], or None).
+
+    ``features`` (the forward's tables) are needed, and their values read, only when ``need_coords``. The table gradients
+    are overwritten (zeroed by the call, the padding row stays zero) and come from float atomics: two runs differ in the
+    last bits."""
+    fdim = _octree_shape(coords, levels, features if need_coords else None, int(feature_dim))
+    N = coords.shape[0]
+    K = fdim if multiscale_sum else fdim * len(levels)
+    if grad_output.dtype != torch.float32:
+        grad_output = grad_output.float()
+    grad_output = grad_output.contiguous()
+    _need_gpu(grad_output)
+    if tuple(grad_output.shape) != (N, K):
+        raise RuntimeError(f"grad_output must be [{N}, {K}], got {tuple(grad_output.shape)}")
+    flags = (_lib.OCTREE_GRAD_FEATURES if need_features else 0) | (_lib.OCTREE_GRAD_COORDS if need_coords else 0)
+    if not flags:
+        return None, None
+    dev = coords.device
+    grads = None
+    if need_features:
+        grads = [torch.empty((li.rows + 1, fdim), dtype=torch.float32, device=dev) for li in levels]
+    grad_coords = torch.empty((N, 3), dtype=torch.float32, device=dev) if need_coords else None
+    L = _lib.lib()
+    la, rows, ci, occ = _octree_arrays(levels)
+    with _on_device(dev):
+        nbytes = int(L.shacira_octree_backward_workspace_bytes(N, len(levels), la, fdim, int(bool(multiscale_sum)), flags))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_octree_backward(N, len(levels), la, fdim, _ptr(coords),
+                                       _plane_array(features) if need_coords else None, rows, ci, occ, _ptr(grad_output),
+                                       int(bool(multiscale_sum)), flags,
+                                       _plane_array(grads) if grads is not None else None, _ptr(grad_coords), _ptr(ws),
+                                       nbytes, _stream(coords))
+    _lib.check(rc, "octree_backward")
+    return grads, grad_coords

@@ -7,6 +7,14 @@ makes of it: ``query``, ``raytrace``, ``raymarch`` ('ray' and 'voxel', octree_as
 ``from_quantized_points`` (pruning, nerf.py:150-185). The reference answers them with kaolin's sparse-octree CUDA
 (un-vendored); here the occupied set is a dense [G, G, G] bit grid walked by the HIP kernels of render.hip.
 ``pidx`` values are Morton indices of the level's cells (the reference's index into its SPC point hierarchy).
+
+Coarser levels (the octree feature grids ask for them): a cell of level l < ``max_level`` is occupied if any cell of
+``max_level`` inside it is. The reduced grids are OR-reductions of the bit grid, cached per level and per device. The cache
+is dropped when ``occupancy_grid`` is replaced by another tensor (a new structure from ``from_quantized_points``, a move to
+another device); code that writes INTO the tensor in place must call ``occupancy_changed()`` itself, as
+``harness.GraphedNerfFitter.after_prune`` does; ``query`` / ``raytrace`` / ``raymarch`` / ``level_points`` take any level in
+0..max_level with the same conventions (``pidx``: Morton index of the cell at that level, -1 if unoccupied or outside).
+``points`` and ``pyramid`` keep describing ``max_level`` only.
 """
 from collections import namedtuple
 
@@ -82,34 +90,76 @@ class OctreeAS(BaseAS):
         grid[q[:, 0], q[:, 1], q[:, 2]] = True
         return cls(level, grid)
 
+    @classmethod
+    def from_pointcloud(cls, pointcloud: torch.Tensor, level: int):
+        """Occupied set = the cells of ``level`` holding a point of ``pointcloud`` [N, 3] in [-1, 1]^3, quantised with
+        ``query``'s floor(G * (x + 1) / 2) and clamped into the grid as kaolin's ``quantize_points`` does (a point on a far
+        face, x = 1, falls into the last cell). Points that are not finite are dropped."""
+        G = 1 << level
+        cell = torch.floor(G * (pointcloud.float() + 1.0) / 2.0)
+        keep = torch.isfinite(cell).all(dim=-1)
+        return cls.from_quantized_points(cell[keep].clamp(0, G - 1).long(), level)
+
+    @classmethod
+    def from_mesh(cls, *args, **kwargs):
+        raise NotImplementedError("OctreeAS.from_mesh needs OBJ loading and surface sampling, which are not part of this "
+                                  "package: sample the surface elsewhere and use from_pointcloud")
+
+    @classmethod
+    def from_spc(cls, *args, **kwargs):
+        raise NotImplementedError("OctreeAS.from_spc reads kaolin's byte octree, which this dense bit grid does not "
+                                  "hold: use from_quantized_points with the cells of the finest level")
+
     def _grid_on(self, device):
         if self.occupancy_grid.device != device:
             self.occupancy_grid = self.occupancy_grid.to(device)
         return self.occupancy_grid
 
     def _level(self, level):
-        if level is not None and level != self.max_level:
-            raise NotImplementedError("only the BLAS level is materialised")
-        return self.max_level
+        if level is None:
+            return self.max_level
+        level = int(level)
+        if not 0 <= level <= self.max_level:
+            raise ValueError(f"level {level} is outside 0..{self.max_level}")
+        return level
+
+    def occupancy_changed(self):
+        """Drop the cached coarser levels: to be called after ``occupancy_grid`` was written in place."""
+        self.__dict__.pop("_coarse", None)
+
+    def occupancy_at(self, level: int, device=None) -> torch.Tensor:
+        """Dense bool [G, G, G] of ``level`` (G = 2^level) on ``device`` (default: where the grid lives)."""
+        level = self._level(level)
+        grid = self._grid_on(device) if device is not None else self.occupancy_grid
+        if level == self.max_level:
+            return grid
+        cache = self.__dict__.get("_coarse")
+        if cache is None or cache[0] is not grid:      # the occupancy was replaced or moved: drop the reductions
+            cache = self._coarse = (grid, {})
+        if level not in cache[1]:
+            G, s = 1 << level, 1 << (self.max_level - level)
+            cache[1][level] = grid.reshape(G, s, G, s, G, s).permute(0, 2, 4, 1, 3, 5).reshape(G, G, G, s * s * s).any(-1)
+        return cache[1][level]
 
     def query(self, coords, level=None, with_parents=False) -> ASQueryResults:
         """pidx [N]: Morton index of the cell holding each point, -1 if that cell is unoccupied or the point lies outside
         the cube (kaolin's float query: cell = floor(G * (x + 1) / 2), out of bounds -> -1)."""
-        if with_parents:
-            raise NotImplementedError("with_parents needs the point hierarchy")
         level = self._level(level)
+        if with_parents:   # [N, level + 1]: column l answers level l (reference octree_grid.py:370)
+            return ASQueryResults(pidx=torch.stack([self.query(coords, l).pidx for l in range(level + 1)], dim=-1))
         G = 1 << level
         cell = torch.floor(G * (coords + 1.0) / 2.0)
         inside = ((cell >= 0) & (cell < G)).all(dim=-1)
         q = torch.nan_to_num(cell, nan=0.0).clamp(0, G - 1).long()
-        occ = inside & self._grid_on(coords.device)[q[:, 0], q[:, 1], q[:, 2]]
+        occ = inside & self.occupancy_at(level, coords.device)[q[:, 0], q[:, 1], q[:, 2]]
         pidx = torch.where(occ, _morton_index(q, level), torch.full_like(q[:, 0], -1))
         return ASQueryResults(pidx=pidx)
 
     def raytrace(self, rays, level=None, with_exit=False) -> ASRaytraceResults:
         from ... import render
         level = self._level(level)
-        ridx, pidx, depth = render.raytrace_dense(rays.origins, rays.dirs, self._grid_on(rays.origins.device), level)
+        ridx, pidx, depth = render.raytrace_dense(rays.origins, rays.dirs, self.occupancy_at(level, rays.origins.device),
+                                                  level)
         return ASRaytraceResults(ridx=ridx, pidx=pidx, depth=depth if with_exit else depth[:, 0:1])
 
     def _raymarch_voxel(self, rays, num_samples, level=None) -> ASRaymarchResults:
@@ -142,11 +192,11 @@ class OctreeAS(BaseAS):
             # fixed-size outputs for a step captured into a HIP graph (harness.GraphedNerfFitter): no count read-back;
             # `last_sample_count` keeps the true count on the device so that the owner can watch for dropped samples
             ridx, samples, depth, deltas, boundary, offsets, self.last_sample_count = render.raymarch_ray(
-                rays.origins, rays.dirs, rays.dist_min, rays.dist_max, self._grid_on(rays.origins.device), level,
+                rays.origins, rays.dirs, rays.dist_min, rays.dist_max, self.occupancy_at(level, rays.origins.device), level,
                 num_samples, capacity=capacity)
         else:
             ridx, samples, depth, deltas, boundary, offsets = render.raymarch_ray(
-                rays.origins, rays.dirs, rays.dist_min, rays.dist_max, self._grid_on(rays.origins.device), level,
+                rays.origins, rays.dirs, rays.dist_min, rays.dist_max, self.occupancy_at(level, rays.origins.device), level,
                 num_samples)
         return ASRaymarchResults(ridx=ridx, samples=samples, depth_samples=depth, deltas=deltas, boundary=boundary,
                                  ray_offsets=offsets)
@@ -159,9 +209,13 @@ class OctreeAS(BaseAS):
         raise TypeError(f"Raymarch sampler type: {raymarch_type} is not supported by OctreeAS.")
 
     def level_points(self, level: int) -> torch.Tensor:
-        if level != self.max_level:
-            raise NotImplementedError("only the dense BLAS level is materialised")
-        return self.points
+        """The occupied cells of ``level`` in Morton order, int16 [cells, 3]."""
+        level = self._level(level)
+        if level == self.max_level:
+            return self.points
+        cells = torch.nonzero(self.occupancy_at(level))
+        order = torch.argsort(_morton_index(cells, level))
+        return cells[order].to(torch.int16)
 
 
 from .aabb_as import AxisAlignedBBoxAS  # noqa: E402  (subclasses OctreeAS above)
