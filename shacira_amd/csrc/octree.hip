@@ -7,12 +7,14 @@
 //                    key (x * S + y) * S + z, so the z and z + 1 corners of a cell edge are rows r and r + 1: four index
 //                    reads and four reads of 2F contiguous floats per sample and level.
 //   forward          one launch, lane per sample, every level; writes the 'cat' or the summed 'sum' row itself
-//   feature backward no scattered global atomics on the coarse levels: the samples are counting-sorted by a block of cells
-//                    of the finest level (cells nest exactly across levels: p_l is p_fine scaled by a power of two); a
-//                    workgroup takes up to kOctChunk samples of one block, one lane per (sample, corner), adds into one
-//                    LDS window per level and flushes the non-zero entries with global adds (consecutive lanes,
-//                    consecutive floats of consecutive rows). A level whose window does not fit adds straight to memory.
+//   feature backward no scattered global atomics on the coarse levels: the samples are counting-sorted (block_sort.h)
+//                    by a block of cells of the finest level (cells nest exactly across levels: p_l is p_fine scaled by a
+//                    power of two); a workgroup takes up to kOctChunk samples of one block, one lane per (sample, corner),
+//                    adds into one LDS window per level and flushes the non-zero entries with global adds (consecutive
+//                    lanes, consecutive floats of consecutive rows). A level whose window does not fit adds straight to
+//                    memory.
 //   coord backward   a gather, lane per sample, no atomics (reads the tables: only when the coordinate gradient is asked)
+#include "block_sort.h"
 #include "internal.h"
 
 namespace shacira {
@@ -20,8 +22,6 @@ namespace shacira {
 constexpr int kOctChunk = 512;             // samples per accumulation unit (one workgroup)
 constexpr int kOctLdsBytes = 64 * 1024;    // LDS budget of one unit's windows (two workgroups per CU at the limit)
 constexpr int kOctMaxCellsLog2 = 4;        // largest block edge: 16 cells of the finest level
-constexpr int kOctMaxBlocksAxis = 64;      // cap of the sort's blocks per axis (262 144 blocks)
-constexpr int kOctLdsBins = 4096;          // histogram / ranking in LDS up to this many blocks, global atomics above
 
 struct OctCell {
     int x, y, z;
@@ -152,21 +152,25 @@ __global__ __launch_bounds__(256) void octree_fwd_kernel(OctreeArgs a, const flo
 }
 
 // ---- feature backward ---------------------------------------------------------------------------------------------------
-// block of a sample: its cell of the finest level (clamped into the cube; not finite -> 0) over the block edge
-__device__ __forceinline__ uint32_t oct_block_of(const OctBwdPlan &bp, const float *coords, int64_t i) {
-    const float g = (float)(1 << bp.fine);
-    const float h = g * 0.5f;
-    uint32_t b = 0;
+// block of a sample (the sort's BlockOf, block_sort.h): its cell of the finest level (clamped into the cube; not finite
+// -> 0) over the block edge, z fastest
+struct OctBlockOf {
+    int32_t fine, cells_log2, nb;
+    __device__ uint32_t operator()(const float *coords, int64_t i) const {
+        const float g = (float)(1 << fine);
+        const float h = g * 0.5f;
+        uint32_t b = 0;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = (coords[i * 3 + d] + 1.0f) * h;
-        int cell = (p >= 0.0f && p < g) ? (int)floorf(p) : (p >= g ? (1 << bp.fine) - 1 : 0);
-        int q = cell >> bp.cells_log2;
-        q = q < 0 ? 0 : (q >= bp.nb ? bp.nb - 1 : q);
-        b = b * (uint32_t)bp.nb + (uint32_t)q;
+        for (int d = 0; d < 3; ++d) {
+            const float p = (coords[i * 3 + d] + 1.0f) * h;
+            int cell = (p >= 0.0f && p < g) ? (int)floorf(p) : (p >= g ? (1 << fine) - 1 : 0);
+            int q = cell >> cells_log2;
+            q = q < 0 ? 0 : (q >= nb ? nb - 1 : q);
+            b = b * (uint32_t)nb + (uint32_t)q;
+        }
+        return b;
     }
-    return b;
-}
+};
 
 // zero the table gradients (padding rows included) and the block histogram
 __global__ __launch_bounds__(256) void octree_zero_kernel(OctreeArgs a, uint32_t *__restrict__ hist, int nbins) {
@@ -181,103 +185,6 @@ __global__ __launch_bounds__(256) void octree_zero_kernel(OctreeArgs a, uint32_t
         for (int64_t e = t0; e < nbins; e += stride) hist[e] = 0u;
 }
 
-// The counting sort by block (the scheme of triplane.hip's plane backward). RANK = false: block histogram; RANK = true: each
-// sample's slot in the sorted order (per-workgroup counts in LDS, one global reservation per (workgroup, block)). The order
-// inside a block is not fixed: the float sums that follow are not either.
-template <bool RANK>
-__global__ __launch_bounds__(256) void octree_bin_kernel(OctBwdPlan bp, const float *__restrict__ coords,
-                                                         uint32_t *__restrict__ counter, uint32_t *__restrict__ sorted,
-                                                         int64_t N) {
-    __shared__ uint32_t lcount[kOctLdsBins];
-    __shared__ uint32_t lbase[kOctLdsBins];
-    const bool lds = bp.nbins <= kOctLdsBins;
-    const int64_t s0 = (int64_t)blockIdx.x * kOctChunk;
-    const int64_t s1 = s0 + kOctChunk < N ? s0 + kOctChunk : N;
-    if (lds) {
-        for (int b = threadIdx.x; b < bp.nbins; b += blockDim.x) lcount[b] = 0u;
-        __syncthreads();
-    }
-    constexpr int kPer = kOctChunk / 256;
-    uint32_t bin[kPer], rank[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-        bin[k] = 0u;
-        rank[k] = 0u;
-        if (i >= s1) continue;
-        bin[k] = oct_block_of(bp, coords, i);
-        if (lds) rank[k] = atomicAdd(&lcount[bin[k]], 1u);
-        else rank[k] = atomicAdd(&counter[bin[k]], 1u);
-    }
-    if (!lds) {
-        if constexpr (RANK) {
-#pragma unroll
-            for (int k = 0; k < kPer; ++k) {
-                const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-                if (i < s1) sorted[rank[k]] = (uint32_t)i;
-            }
-        }
-        return;
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < bp.nbins; b += blockDim.x) {
-        const uint32_t n = lcount[b];
-        if (n) lbase[b] = atomicAdd(&counter[b], n);
-    }
-    if constexpr (RANK) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-            if (i < s1) sorted[lbase[bin[k]] + rank[k]] = (uint32_t)i;
-        }
-    }
-}
-
-// one workgroup: exclusive scan of the histogram -> start[b] (and the ranking cursor, the same values), units of kOctChunk
-// samples per block -> ustart[b]; ustart[nbins] = number of units
-__global__ __launch_bounds__(1024) void octree_scan_kernel(int nbins, uint32_t *__restrict__ hist,
-                                                           uint32_t *__restrict__ start, uint32_t *__restrict__ ustart) {
-    __shared__ uint32_t ws[2][1024];
-    const int T = 1024;
-    const int per = (nbins + T - 1) / T;
-    const int b0 = std::min((int)threadIdx.x * per, nbins);
-    const int b1 = b0 + per < nbins ? b0 + per : nbins;
-    uint32_t s = 0, u = 0;
-    for (int b = b0; b < b1; ++b) {
-        s += hist[b];
-        u += (hist[b] + kOctChunk - 1) / kOctChunk;
-    }
-    ws[0][threadIdx.x] = s;
-    ws[1][threadIdx.x] = u;
-    __syncthreads();
-    for (int off = 1; off < T; off <<= 1) {   // Hillis-Steele inclusive scan
-        uint32_t vs = 0, vu = 0;
-        if ((int)threadIdx.x >= off) {
-            vs = ws[0][threadIdx.x - off];
-            vu = ws[1][threadIdx.x - off];
-        }
-        __syncthreads();
-        ws[0][threadIdx.x] += vs;
-        ws[1][threadIdx.x] += vu;
-        __syncthreads();
-    }
-    s = ws[0][threadIdx.x] - s;
-    u = ws[1][threadIdx.x] - u;
-    for (int b = b0; b < b1; ++b) {
-        const uint32_t n = hist[b];
-        start[b] = s;
-        ustart[b] = u;
-        hist[b] = s;   // the ranking pass's cursor
-        s += n;
-        u += (n + kOctChunk - 1) / kOctChunk;
-    }
-    if (threadIdx.x == T - 1) {
-        start[nbins] = ws[0][T - 1];
-        ustart[nbins] = ws[1][T - 1];
-    }
-}
-
 // A unit = up to kOctChunk sorted samples of one block. Zero the windows; one lane per (sample, corner) adds w_k * g into
 // the level's window (a level without one, and a corner outside its window, add to memory); flush the non-zero entries.
 __global__ __launch_bounds__(256) void octree_accum_kernel(OctreeArgs a, OctBwdPlan bp, const float *__restrict__ coords,
@@ -286,17 +193,9 @@ __global__ __launch_bounds__(256) void octree_accum_kernel(OctreeArgs a, OctBwdP
                                                            const uint32_t *__restrict__ start,
                                                            const uint32_t *__restrict__ ustart) {
     extern __shared__ float win[];
-    const uint32_t unit = blockIdx.x;
-    if (unit >= ustart[bp.nbins]) return;
-    int lo = 0, hi = bp.nbins - 1;   // the block whose unit range holds `unit`: last b with ustart[b] <= unit
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (ustart[mid] <= unit) lo = mid;
-        else hi = mid - 1;
-    }
-    const int b = lo;
-    const uint32_t s0 = start[b] + (unit - ustart[b]) * (uint32_t)kOctChunk;
-    const uint32_t s1 = s0 + kOctChunk < start[b + 1] ? s0 + kOctChunk : start[b + 1];
+    int b;
+    uint32_t s0, s1;
+    if (!block_sort_unit<kOctChunk>(blockIdx.x, bp.nbins, start, ustart, b, s0, s1)) return;
     // the block's first cell of the finest level, per axis
     const int org[3] = {(b / (bp.nb * bp.nb)) << bp.cells_log2, ((b / bp.nb) % bp.nb) << bp.cells_log2,
                         (b % bp.nb) << bp.cells_log2};
@@ -435,8 +334,8 @@ void octree_backward_plan(const OctreeArgs &a, int sum, OctBwdPlan &bp) {
     int c = std::min(fine, kOctMaxCellsLog2);   // the largest block whose windows all fit ...
     while (c > 0 && total(c) > budget) --c;
     int nb = 1 << (fine - c);
-    if (nb > kOctMaxBlocksAxis) {               // ... unless that makes more blocks than the sort takes
-        nb = kOctMaxBlocksAxis;
+    if (nb > kBlockSortMaxBlocksAxis) {         // ... unless that makes more blocks than the sort takes
+        nb = kBlockSortMaxBlocksAxis;
         c = fine - 6;
     }
     bp.fine = fine;
@@ -465,13 +364,11 @@ void octree_backward_plan(const OctreeArgs &a, int sum, OctBwdPlan &bp) {
     bp.wtotal = (int32_t)used;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t octree_backward_workspace(const OctreeArgs &a, int sum, int64_t n) {
     if (n <= 0) return 0;
     OctBwdPlan bp;
     octree_backward_plan(a, sum, bp);
-    return 3 * align256(((size_t)bp.nbins + 1) * sizeof(uint32_t)) + align256((size_t)n * sizeof(uint32_t));
+    return block_sort_workspace_bytes(bp.nbins, n);
 }
 
 hipError_t octree_backward_dispatch(const OctreeArgs &a, const float *coords, const float *grad_out, int sum,
@@ -489,26 +386,18 @@ hipError_t octree_backward_dispatch(const OctreeArgs &a, const float *coords, co
     if (!features) return hipSuccess;
     OctBwdPlan bp;
     octree_backward_plan(a, sum, bp);
-    char *w = static_cast<char *>(workspace);
-    const size_t binb = align256(((size_t)bp.nbins + 1) * sizeof(uint32_t));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w);
-    uint32_t *start = reinterpret_cast<uint32_t *>(w + binb);
-    uint32_t *ustart = reinterpret_cast<uint32_t *>(w + 2 * binb);
-    uint32_t *sorted = reinterpret_cast<uint32_t *>(w + 3 * binb);
-    hipLaunchKernelGGL(octree_zero_kernel, dim3(1024), dim3(256), 0, s, a, hist, bp.nbins);
-    const uint32_t chunks = (uint32_t)((n + kOctChunk - 1) / kOctChunk);
-    hipLaunchKernelGGL((octree_bin_kernel<false>), dim3(chunks), dim3(256), 0, s, bp, coords, hist, nullptr, n);
-    hipLaunchKernelGGL(octree_scan_kernel, dim3(1), dim3(1024), 0, s, bp.nbins, hist, start, ustart);
-    hipLaunchKernelGGL((octree_bin_kernel<true>), dim3(chunks), dim3(256), 0, s, bp, coords, hist, sorted, n);
+    const BlockSortBuffers buf = block_sort_carve(workspace, bp.nbins);
+    hipLaunchKernelGGL(octree_zero_kernel, dim3(1024), dim3(256), 0, s, a, buf.hist, bp.nbins);
+    const uint32_t units =
+        block_sort_launch<kOctChunk>(OctBlockOf{bp.fine, bp.cells_log2, bp.nb}, coords, n, bp.nbins, buf, s);
     static PerDeviceOnce once;
     if (hipError_t e = once.run([] {
             return hipFuncSetAttribute(reinterpret_cast<const void *>(octree_accum_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kOctLdsBytes);
         }))
         return e;
-    const uint32_t units = chunks + (uint32_t)bp.nbins;   // >= the number of units (each block rounds up once)
     hipLaunchKernelGGL(octree_accum_kernel, dim3(units), dim3(256), (size_t)bp.wtotal * sizeof(float), s, a, bp, coords,
-                       grad_out, sorted, start, ustart);
+                       grad_out, buf.sorted, buf.start, buf.ustart);
     return hipGetLastError();
 }
 

@@ -5,15 +5,17 @@
 //   forward          one launch, lane per sample, every selected LOD and all three planes; reads an HWC copy of the
 //                    planes that one transpose launch writes into the workspace (the rule, 3x faster), or with option
 //                    "triplane_layout" = 0 the NCHW parameters in place (F loads per corner); profiles/triplane.md
-//   plane backward   no scattered global atomics on the bulk: the samples are counting-sorted by a 3-D block of the
-//                    reflected cube (one sort serves all three planes: a block's projection on each plane is a square
-//                    window); a workgroup takes up to kTriChunk samples of one block, accumulates each LOD's three windows
-//                    in LDS and flushes the non-zero texels with coalesced global adds. Corners that miss the window
-//                    (rounding at a block face) and LODs whose windows exceed the LDS budget add straight to global memory.
+//   plane backward   no scattered global atomics on the bulk: the samples are counting-sorted (block_sort.h) by a 3-D
+//                    block of the reflected cube (one sort serves all three planes: a block's projection on each plane is
+//                    a square window); a workgroup takes up to kTriChunk samples of one block, accumulates each LOD's
+//                    three windows in LDS and flushes the non-zero texels with coalesced global adds. Corners that miss
+//                    the window (rounding at a block face) and LODs whose windows exceed the LDS budget add straight to
+//                    global memory.
 //   coord backward   a gather, lane per sample, no atomics (reads the planes: only when the coordinate gradient is asked)
 #include <cfloat>
 #include <climits>
 
+#include "block_sort.h"
 #include "internal.h"
 
 namespace shacira {
@@ -23,8 +25,6 @@ namespace shacira {
 #endif
 constexpr int kTriChunk = SHACIRA_TRI_CHUNK;   // samples per accumulation unit (one workgroup); profiles/triplane.md
 constexpr int kTriLdsBytes = 64 * 1024;    // LDS budget of the three windows of one LOD (two workgroups per CU)
-constexpr int kTriMaxBlocksAxis = 64;      // cap of the sort's blocks per axis (262 144 blocks)
-constexpr int kTriLdsBins = 4096;          // histogram / ranking in LDS up to this many blocks, global atomics above
 
 // ---- the index math of ATen/native/cuda/GridSampler.cuh (align_corners = true, reflection), fp32 --------------------------
 __device__ __forceinline__ float tri_unnormalize(float c, int size) { return ((c + 1.f) / 2) * (float)(size - 1); }
@@ -201,20 +201,23 @@ __global__ __launch_bounds__(256) void triplane_to_hwc_kernel(TriplaneArgs a, fl
 }
 
 // ---- plane backward ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t tri_block_of(const TriplaneArgs &a, const TriBwdPlan &bp, const float *coords,
-                                                  int64_t i) {
-    uint32_t b = 0, mul = 1;
+// block of a sample (the sort's BlockOf, block_sort.h): its texel cell of the finest LOD over the block edge, x fastest
+struct TriBlockOf {
+    int32_t sort_side, cells, nb;
+    __device__ uint32_t operator()(const float *coords, int64_t i) const {
+        uint32_t b = 0, mul = 1;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        float g;
-        const float x = tri_source_index_grad(coords[i * 3 + d], bp.sort_side, &g);
-        int q = x < 0.0f ? 0 : (int)x / bp.cells;
-        q = q < 0 ? 0 : (q >= bp.nb ? bp.nb - 1 : q);
-        b += (uint32_t)q * mul;
-        mul *= (uint32_t)bp.nb;
+        for (int d = 0; d < 3; ++d) {
+            float g;
+            const float x = tri_source_index_grad(coords[i * 3 + d], sort_side, &g);
+            int q = x < 0.0f ? 0 : (int)x / cells;
+            q = q < 0 ? 0 : (q >= nb ? nb - 1 : q);
+            b += (uint32_t)q * mul;
+            mul *= (uint32_t)nb;
+        }
+        return b;
     }
-    return b;
-}
+};
 
 // zero the plane gradients and the block histogram
 __global__ __launch_bounds__(256) void triplane_zero_kernel(TriplaneArgs a, uint32_t *__restrict__ hist, int nbins) {
@@ -229,103 +232,6 @@ __global__ __launch_bounds__(256) void triplane_zero_kernel(TriplaneArgs a, uint
         for (int64_t e = t0; e < nbins; e += stride) hist[e] = 0u;
 }
 
-// RANK = false: block histogram; RANK = true: each sample's slot in the sorted order (per-workgroup counts in LDS, one global
-// reservation per (workgroup, block)). Order inside a block is not fixed: the float sums that follow are not either.
-template <bool RANK>
-__global__ __launch_bounds__(256) void triplane_bin_kernel(TriplaneArgs a, TriBwdPlan bp, const float *__restrict__ coords,
-                                                           uint32_t *__restrict__ counter, uint32_t *__restrict__ sorted,
-                                                           int64_t N) {
-    __shared__ uint32_t lcount[kTriLdsBins];
-    __shared__ uint32_t lbase[kTriLdsBins];
-    const bool lds = bp.nbins <= kTriLdsBins;
-    const int64_t per_block = (int64_t)kTriChunk;
-    const int64_t s0 = (int64_t)blockIdx.x * per_block;
-    const int64_t s1 = s0 + per_block < N ? s0 + per_block : N;
-    if (lds) {
-        for (int b = threadIdx.x; b < bp.nbins; b += blockDim.x) lcount[b] = 0u;
-        __syncthreads();
-    }
-    constexpr int kPer = kTriChunk / 256;
-    uint32_t bin[kPer], rank[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-        bin[k] = 0u;
-        rank[k] = 0u;
-        if (i >= s1) continue;
-        bin[k] = tri_block_of(a, bp, coords, i);
-        if (lds) rank[k] = atomicAdd(&lcount[bin[k]], 1u);
-        else rank[k] = atomicAdd(&counter[bin[k]], 1u);
-    }
-    if (!lds) {
-        if constexpr (RANK) {
-#pragma unroll
-            for (int k = 0; k < kPer; ++k) {
-                const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-                if (i < s1) sorted[rank[k]] = (uint32_t)i;
-            }
-        }
-        return;
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < bp.nbins; b += blockDim.x) {
-        const uint32_t n = lcount[b];
-        if (n) lbase[b] = atomicAdd(&counter[b], n);
-    }
-    if constexpr (RANK) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int64_t i = s0 + (int64_t)k * 256 + threadIdx.x;
-            if (i < s1) sorted[lbase[bin[k]] + rank[k]] = (uint32_t)i;
-        }
-    }
-}
-
-// one workgroup: exclusive scan of the histogram -> start[b] (and the ranking cursor, the same values), units of kTriChunk
-// samples per block -> ustart[b]; ustart[nbins] = number of units
-__global__ __launch_bounds__(1024) void triplane_scan_kernel(TriBwdPlan bp, uint32_t *__restrict__ hist,
-                                                             uint32_t *__restrict__ start, uint32_t *__restrict__ ustart) {
-    __shared__ uint32_t ws[2][1024];
-    const int T = 1024;
-    const int per = (bp.nbins + T - 1) / T;
-    const int b0 = threadIdx.x * per;
-    const int b1 = b0 + per < bp.nbins ? b0 + per : bp.nbins;
-    uint32_t s = 0, u = 0;
-    for (int b = b0; b < b1; ++b) {
-        s += hist[b];
-        u += (hist[b] + kTriChunk - 1) / kTriChunk;
-    }
-    ws[0][threadIdx.x] = s;
-    ws[1][threadIdx.x] = u;
-    __syncthreads();
-    for (int off = 1; off < T; off <<= 1) {   // Hillis-Steele inclusive scan
-        uint32_t vs = 0, vu = 0;
-        if ((int)threadIdx.x >= off) {
-            vs = ws[0][threadIdx.x - off];
-            vu = ws[1][threadIdx.x - off];
-        }
-        __syncthreads();
-        ws[0][threadIdx.x] += vs;
-        ws[1][threadIdx.x] += vu;
-        __syncthreads();
-    }
-    s = ws[0][threadIdx.x] - s;
-    u = ws[1][threadIdx.x] - u;
-    for (int b = b0; b < b1; ++b) {
-        const uint32_t n = hist[b];
-        start[b] = s;
-        ustart[b] = u;
-        hist[b] = s;   // the ranking pass's cursor
-        s += n;
-        u += (n + kTriChunk - 1) / kTriChunk;
-    }
-    if (threadIdx.x == T - 1) {
-        start[bp.nbins] = ws[0][T - 1];
-        ustart[bp.nbins] = ws[1][T - 1];
-    }
-}
-
 // A unit = up to kTriChunk sorted samples of one block. Per LOD: zero the three windows, LDS-add every corner that falls
 // inside its window (the rest: global adds), flush non-zero texels with global adds ([plane][channel][y][x]: consecutive
 // lanes, consecutive x).
@@ -335,17 +241,9 @@ __global__ __launch_bounds__(256) void triplane_accum_kernel(TriplaneArgs a, Tri
                                                              const uint32_t *__restrict__ start,
                                                              const uint32_t *__restrict__ ustart, int64_t N) {
     extern __shared__ float win[];
-    const uint32_t unit = blockIdx.x;
-    if (unit >= ustart[bp.nbins]) return;
-    int lo = 0, hi = bp.nbins - 1;   // the block whose unit range holds `unit`: last b with ustart[b] <= unit
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (ustart[mid] <= unit) lo = mid;
-        else hi = mid - 1;
-    }
-    const int b = lo;
-    const uint32_t s0 = start[b] + (unit - ustart[b]) * (uint32_t)kTriChunk;
-    const uint32_t s1 = s0 + kTriChunk < start[b + 1] ? s0 + kTriChunk : start[b + 1];
+    int b;
+    uint32_t s0, s1;
+    if (!block_sort_unit<kTriChunk>(blockIdx.x, bp.nbins, start, ustart, b, s0, s1)) return;
     const int bq[3] = {b % bp.nb, (b / bp.nb) % bp.nb, b / (bp.nb * bp.nb)};
     const int F = a.fdim;
     const int gstride = bp.sum ? 3 * F : a.num_lods * 3 * F;
@@ -529,7 +427,7 @@ void triplane_backward_plan(const TriplaneArgs &a, int sum, TriBwdPlan &bp) {
     int cells = rmax;   // largest power-of-two block edge (texels of the finest LOD) whose windows fit
     while (cells > 1 && !fits(cells + 1)) cells >>= 1;
     int nb = rmax / cells;
-    if (nb > kTriMaxBlocksAxis) nb = kTriMaxBlocksAxis;
+    if (nb > kBlockSortMaxBlocksAxis) nb = kBlockSortMaxBlocksAxis;
     bp.nb = nb;
     bp.nbins = nb * nb * nb;
     bp.sort_side = rmax + 1;
@@ -542,13 +440,11 @@ void triplane_backward_plan(const TriplaneArgs &a, int sum, TriBwdPlan &bp) {
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t triplane_backward_workspace(const TriplaneArgs &a, int sum, int64_t n) {
     if (n <= 0) return 0;
     TriBwdPlan bp;
     triplane_backward_plan(a, sum, bp);
-    return 3 * align256(((size_t)bp.nbins + 1) * sizeof(uint32_t)) + align256((size_t)n * sizeof(uint32_t));
+    return block_sort_workspace_bytes(bp.nbins, n);
 }
 
 hipError_t triplane_backward_dispatch(const TriplaneArgs &a, const float *coords, const float *grad_out, int sum,
@@ -566,17 +462,10 @@ hipError_t triplane_backward_dispatch(const TriplaneArgs &a, const float *coords
     if (!planes) return hipSuccess;
     TriBwdPlan bp;
     triplane_backward_plan(a, sum, bp);
-    char *w = static_cast<char *>(workspace);
-    const size_t binb = align256(((size_t)bp.nbins + 1) * sizeof(uint32_t));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w);
-    uint32_t *start = reinterpret_cast<uint32_t *>(w + binb);
-    uint32_t *ustart = reinterpret_cast<uint32_t *>(w + 2 * binb);
-    uint32_t *sorted = reinterpret_cast<uint32_t *>(w + 3 * binb);
-    hipLaunchKernelGGL(triplane_zero_kernel, dim3(1024), dim3(256), 0, s, a, hist, bp.nbins);
-    const uint32_t chunks = (uint32_t)((n + kTriChunk - 1) / kTriChunk);
-    hipLaunchKernelGGL((triplane_bin_kernel<false>), dim3(chunks), dim3(256), 0, s, a, bp, coords, hist, nullptr, n);
-    hipLaunchKernelGGL(triplane_scan_kernel, dim3(1), dim3(1024), 0, s, bp, hist, start, ustart);
-    hipLaunchKernelGGL((triplane_bin_kernel<true>), dim3(chunks), dim3(256), 0, s, a, bp, coords, hist, sorted, n);
+    const BlockSortBuffers buf = block_sort_carve(workspace, bp.nbins);
+    hipLaunchKernelGGL(triplane_zero_kernel, dim3(1024), dim3(256), 0, s, a, buf.hist, bp.nbins);
+    const uint32_t units =
+        block_sort_launch<kTriChunk>(TriBlockOf{bp.sort_side, bp.cells, bp.nb}, coords, n, bp.nbins, buf, s);
     int wmax = 0;
     for (int l = 0; l < a.num_lods; ++l) wmax = std::max(wmax, bp.win[l]);
     const size_t lds = (size_t)3 * wmax * wmax * a.fdim * sizeof(float);
@@ -586,9 +475,8 @@ hipError_t triplane_backward_dispatch(const TriplaneArgs &a, const float *coords
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kTriLdsBytes);
         }))
         return e;
-    const uint32_t units = chunks + (uint32_t)bp.nbins;   // >= the number of units (each block rounds up once)
-    hipLaunchKernelGGL(triplane_accum_kernel, dim3(units), dim3(256), lds, s, a, bp, coords, grad_out, sorted, start,
-                       ustart, n);
+    hipLaunchKernelGGL(triplane_accum_kernel, dim3(units), dim3(256), lds, s, a, bp, coords, grad_out, buf.sorted,
+                       buf.start, buf.ustart, n);
     return hipGetLastError();
 }
 

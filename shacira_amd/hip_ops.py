@@ -25,6 +25,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _ptr_array(tensors):     # per-plane / per-level pointers, copied into the kernel arguments by the library
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 @functools.lru_cache(maxsize=64)
 def _res_array(resolutions):
     return (ctypes.c_int32 * len(resolutions))(*resolutions)
@@ -55,6 +59,24 @@ def _check_coords(dim, coords):
     if coords.dim() != 2 or coords.shape[1] != dim or not coords.is_contiguous():
         raise RuntimeError(f"shacira_amd: coords must be a contiguous [N, {dim}] tensor for the {dim}-D operator, got "
                            f"{tuple(coords.shape)}")
+
+
+def _check_float_coords(dim, coords, *others):
+    _need_gpu(coords, *others)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float for coords")  # data_ptr<float>() in the reference
+    _check_coords(dim, coords)      # [N, dim], contiguous: the kernels read dim floats per sample
+
+
+def _check_grad_output(grad_output, N, K):
+    """``grad_output`` as the contiguous fp32 [N, K] tensor on the device that the triplane / octree backward reads."""
+    if grad_output.dtype != torch.float32:
+        grad_output = grad_output.float()
+    grad_output = grad_output.contiguous()
+    _need_gpu(grad_output)
+    if tuple(grad_output.shape) != (N, K):
+        raise RuntimeError(f"grad_output must be [{N}, {K}], got {tuple(grad_output.shape)}")
+    return grad_output
 
 
 # ---- scratch memory: one grow-only buffer per (device, stream, host thread) -----------------------------------------------
@@ -189,10 +211,7 @@ def _dtype_code(t):
 
 
 def _hashgrid_forward(dim, coords, codebook, codebook_first_idx, resolution, codebook_bitwidth, plan=None, plan_ready=False):
-    _need_gpu(coords, codebook, codebook_first_idx)
-    if coords.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for coords")  # data_ptr<float>() in the reference
-    _check_coords(dim, coords)
+    _check_float_coords(dim, coords, codebook, codebook_first_idx)
     res = tuple(int(r) for r in resolution)
     N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
     feats = torch.empty((N, F * len(res)), dtype=codebook.dtype, device=codebook.device)
@@ -281,10 +300,7 @@ def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_
     """Gradient of the features with respect to the coordinates: fp32 [N, dim] (include/shacira_hip.h,
     shacira_hashgrid_coords_backward). ``codebook`` is the table the forward read; ``grad_output`` [N, L*F] is taken in
     the table's dtype; ``plan``: the buffer the forward of the SAME coordinate batch filled, or None."""
-    _need_gpu(coords, grad_output, codebook, codebook_first_idx)
-    if coords.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for coords")
-    _check_coords(dim, coords)
+    _check_float_coords(dim, coords, grad_output, codebook, codebook_first_idx)
     res = tuple(int(r) for r in resolution)
     N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
     dt = _dtype_code(codebook)
@@ -313,10 +329,7 @@ def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_
 
 def hashgrid_debug_corners(dim, coords, resolution, codebook_bitwidth):
     """Test hook: (rows int32 [N, L, 2^dim], weights fp32 [N, L, 2^dim]) exactly as the kernels compute them."""
-    _need_gpu(coords)
-    if coords.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for coords")
-    _check_coords(dim, coords)      # [N, dim], contiguous: the kernel reads dim floats per sample
+    _check_float_coords(dim, coords)
     res = tuple(int(r) for r in resolution)
     N = coords.shape[0]
     rows = torch.empty((N, len(res), 1 << dim), dtype=torch.int32, device=coords.device)
@@ -711,15 +724,8 @@ def latent_symbol_counts(latent):
 
 
 # ---- triplanes (include/shacira_hip.h, shacira_triplane_*) -----------------------------------------------------------------
-def _plane_array(planes):
-    return (ctypes.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
-
-
 def _triplane_shape(coords, lods, planes):
-    _need_gpu(coords, *planes)
-    if coords.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for coords")
-    _check_coords(3, coords)
+    _check_float_coords(3, coords, *planes)
     lods = tuple(int(l) for l in lods)
     if len(planes) != 3 * len(lods):
         raise RuntimeError(f"shacira_amd: {len(lods)} LODs need {3 * len(lods)} planes, got {len(planes)}")
@@ -747,7 +753,7 @@ def triplane_forward(coords, lods, planes, multiscale_sum):
     with _on_device(coords.device):
         nbytes = int(L.shacira_triplane_forward_workspace_bytes(N, len(lods), la, fdim, int(bool(multiscale_sum))))
         ws = _workspace(coords.device, nbytes)
-        rc = L.shacira_triplane_forward(N, len(lods), la, fdim, _ptr(coords), _plane_array(planes),
+        rc = L.shacira_triplane_forward(N, len(lods), la, fdim, _ptr(coords), _ptr_array(planes),
                                         int(bool(multiscale_sum)), _ptr(feats), _ptr(ws), nbytes, _stream(coords))
     _lib.check(rc, "triplane_forward")
     return feats
@@ -764,20 +770,12 @@ def triplane_backward(coords, lods, feature_dim, grad_output, multiscale_sum, pl
     if need_coords:
         lods, fdim = _triplane_shape(coords, lods, planes)
     else:
-        _need_gpu(coords)
-        if coords.dtype != torch.float32:
-            raise RuntimeError("expected scalar type Float for coords")
-        _check_coords(3, coords)
+        _check_float_coords(3, coords)
         if min(lods, default=-1) < 0:
             raise RuntimeError("shacira_amd: triplane LODs must be >= 0")
     N = coords.shape[0]
     K = 3 * fdim if multiscale_sum else 3 * fdim * len(lods)
-    if grad_output.dtype != torch.float32:
-        grad_output = grad_output.float()
-    grad_output = grad_output.contiguous()
-    _need_gpu(grad_output)
-    if tuple(grad_output.shape) != (N, K):
-        raise RuntimeError(f"grad_output must be [{N}, {K}], got {tuple(grad_output.shape)}")
+    grad_output = _check_grad_output(grad_output, N, K)
     flags = (_lib.TRIPLANE_GRAD_PLANES if need_planes else 0) | (_lib.TRIPLANE_GRAD_COORDS if need_coords else 0)
     if not flags:
         return None, None
@@ -794,9 +792,9 @@ def triplane_backward(coords, lods, feature_dim, grad_output, multiscale_sum, pl
                                                                  flags))
         ws = _workspace(dev, nbytes)
         rc = L.shacira_triplane_backward(N, len(lods), la, fdim, _ptr(coords),
-                                         _plane_array(planes) if need_coords else None, _ptr(grad_output),
+                                         _ptr_array(planes) if need_coords else None, _ptr(grad_output),
                                          int(bool(multiscale_sum)), flags,
-                                         _plane_array(grads) if grads is not None else None, _ptr(grad_coords),
+                                         _ptr_array(grads) if grads is not None else None, _ptr(grad_coords),
                                          _ptr(ws), nbytes, _stream(coords))
     _lib.check(rc, "triplane_backward")
     return grads, grad_coords
@@ -805,10 +803,7 @@ def triplane_backward(coords, lods, feature_dim, grad_output, multiscale_sum, pl
 # ---- octree grids (include/shacira_hip.h, shacira_octree_*) ----------------------------------------------------------------
 def _octree_shape(coords, levels, tables, fdim=None):
     """``levels``: one ``wisp.ops.octree.OctreeLevelIndex`` per level, on the coordinates' device."""
-    _need_gpu(coords)
-    if coords.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for coords")
-    _check_coords(3, coords)
+    _check_float_coords(3, coords)
     if not levels:
         raise RuntimeError("shacira_amd: the octree lookup needs at least one level")
     if tables is not None:
@@ -853,7 +848,7 @@ def octree_forward(coords, levels, tables, multiscale_sum):
     with _on_device(coords.device):
         nbytes = int(L.shacira_octree_forward_workspace_bytes(N, len(levels), la, fdim, int(bool(multiscale_sum))))
         ws = _workspace(coords.device, nbytes)
-        rc = L.shacira_octree_forward(N, len(levels), la, fdim, _ptr(coords), _plane_array(tables), rows, ci, occ,
+        rc = L.shacira_octree_forward(N, len(levels), la, fdim, _ptr(coords), _ptr_array(tables), rows, ci, occ,
                                       int(bool(multiscale_sum)), _ptr(feats), _ptr(ws), nbytes, _stream(coords))
     _lib.check(rc, "octree_forward")
     return feats
@@ -869,12 +864,7 @@ def octree_backward(coords, levels, feature_dim, grad_output, multiscale_sum, fe
     fdim = _octree_shape(coords, levels, features if need_coords else None, int(feature_dim))
     N = coords.shape[0]
     K = fdim if multiscale_sum else fdim * len(levels)
-    if grad_output.dtype != torch.float32:
-        grad_output = grad_output.float()
-    grad_output = grad_output.contiguous()
-    _need_gpu(grad_output)
-    if tuple(grad_output.shape) != (N, K):
-        raise RuntimeError(f"grad_output must be [{N}, {K}], got {tuple(grad_output.shape)}")
+    grad_output = _check_grad_output(grad_output, N, K)
     flags = (_lib.OCTREE_GRAD_FEATURES if need_features else 0) | (_lib.OCTREE_GRAD_COORDS if need_coords else 0)
     if not flags:
         return None, None
@@ -889,9 +879,9 @@ def octree_backward(coords, levels, feature_dim, grad_output, multiscale_sum, fe
         nbytes = int(L.shacira_octree_backward_workspace_bytes(N, len(levels), la, fdim, int(bool(multiscale_sum)), flags))
         ws = _workspace(dev, nbytes)
         rc = L.shacira_octree_backward(N, len(levels), la, fdim, _ptr(coords),
-                                       _plane_array(features) if need_coords else None, rows, ci, occ, _ptr(grad_output),
+                                       _ptr_array(features) if need_coords else None, rows, ci, occ, _ptr(grad_output),
                                        int(bool(multiscale_sum)), flags,
-                                       _plane_array(grads) if grads is not None else None, _ptr(grad_coords), _ptr(ws),
+                                       _ptr_array(grads) if grads is not None else None, _ptr(grad_coords), _ptr(ws),
                                        nbytes, _stream(coords))
     _lib.check(rc, "octree_backward")
     return grads, grad_coords
