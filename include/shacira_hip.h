@@ -224,6 +224,64 @@ SHACIRA_API int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, in
                                                  size_t workspace_bytes, void *stream);
 
 /*
+ * Backward of the coordinate backward (ABI 11, additive): what a loss on the coordinate gradient (eikonal, normal
+ * consistency, gradient matching) needs. The node differentiated is shacira_hashgrid_coords_backward above,
+ *   gc[n,a] = sum_l s_l,a * sum_f g[n,l,f] * sum_k sigma_a(k) W_a(k) t[k,f]
+ * in that comment's symbols, with sigma_a(k) = +1 if corner k's bit for axis a is set and -1 otherwise (the pair sum written
+ * over single corners), W_a(k) = prod_{c != a} w_c(k) and W_ab(k) = prod_{c != a,b} w_c(k) (1 in 2-D), w_c(k) = frac if corner
+ * k's bit for axis c is set, 1 - frac otherwise. Given v = dL/dgc (grad_grad_coords, fp32 [num_coords, dim]):
+ *
+ *   (1) grad_grad_output[n,l,f] = sum_a v_a s_l,a sum_k sigma_a(k) W_a(k) t[k,f]
+ *       the directional derivative of the features along v: a gather (coords, v, the table; not g)
+ *   (2) grad_codebook[first_l + row_k, f] += g[n,l,f] * sum_a v_a s_l,a sigma_a(k) W_a(k)
+ *       the addresses of shacira_hashgrid_backward with the corner weight replaced by its directional derivative: a
+ *       scatter-add (coords, v, g; not the table's values). Overwritten: the call zeroes it first, out-of-table corners are
+ *       never touched
+ *   (3) grad_coords[n,b] = sum_l sum_{a != b} v_a s_l,a s_l,b sum_f g[n,l,f] sum_k sigma_a(k) sigma_b(k) W_ab(k) t[k,f]
+ *       the mixed second derivatives: a gather, fp32 [num_coords, dim], overwritten. The pure second derivatives are zero
+ *       inside a cell, and the derivative of the slope s (zero almost everywhere) is taken as zero
+ *
+ * fp32 arithmetic on the forward's fp64 coordinate transform, explicit fmaf (-ffp-contract=off). (1) and (3) are ONE
+ * expression tree each, evaluated by every kernel variant, so a sample's result depends on that sample alone and calls agree
+ * bit for bit across runs, sample order and planned or plain invocation. Per level l, c_a = v_a * s_l,a, corner k: bit
+ * dim-1-a -> axis a:
+ *   (1) D_f[a] as in shacira_hashgrid_coords_backward; R_f = c_0 * D_f[0], then fmaf(c_a, D_f[a], R_f) for a ascending;
+ *       grad_grad_output[n,l,f] = R_f (fp16: rounded once from the finished fp32 value)
+ *   (3) q(kc) = (t[a1 b1 kc] - t[a1 b0 kc]) - (t[a0 b1 kc] - t[a0 b0 kc]) for the pair a < b, kc the bit of the third axis c;
+ *       M_f[ab] = q (2-D), fmaf(q(1), frac_c, q(0) * (1 - frac_c)) (3-D);
+ *       P[ab] = g_0 * M_0[ab], then fmaf(g_f, M_f[ab], P[ab]) for f ascending;
+ *       inner[b] = c_a * P[ab] for the first a != b, then fmaf(c_a, P[ab], inner[b]) for the next (a ascending);
+ *       grad[b] = 0, then fmaf(s_l,b, inner[b], grad[b]) for l ascending
+ * (2) sums with float atomics and is reproducible only to the bar of shacira_hashgrid_backward.
+ *
+ * Table dtypes: fp32 and fp16 (values widened, grad_output read as half, grad_grad_output written as half, grad_codebook
+ * accumulated in an fp32 image in the workspace and rounded once). fp64 tables are first order only: SHACIRA_EDTYPE.
+ *
+ *   grad_grad_coords   v, fp32 [num_coords, dim]
+ *   grad_grad_output   out [num_coords, num_lods*feature_dim] of `dtype`, or NULL
+ *   grad_codebook      out [table_rows, feature_dim] of `dtype`, or NULL
+ *   grad_coords        out fp32 [num_coords, dim], or NULL
+ *   A NULL output is not computed; at least one must be given. codebook may be NULL only when grad_codebook is the sole
+ *   output, grad_output only when grad_grad_output is the sole output.
+ *   plan               as for shacira_hashgrid_coords_backward
+ *   workspace          shacira_hashgrid_coords_backward2_workspace_bytes(...) bytes: the fp32 image of a half table (needed only
+ *                      when grad_codebook is requested), 0 for fp32 tables
+ * Validation happens before any HIP call, with the codes of shacira_hashgrid_forward (SHACIRA_EWORKSPACE for a short workspace
+ * or plan). num_coords == 0 returns 0 after zeroing a requested grad_codebook. No host synchronisation and no allocation: safe
+ * to capture into a graph.
+ */
+SHACIRA_API size_t shacira_hashgrid_coords_backward2_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                                     int codebook_bitwidth, const int32_t *resolutions_host,
+                                                                     int64_t table_rows, int dtype);
+SHACIRA_API int shacira_hashgrid_coords_backward2(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                  int codebook_bitwidth, const int32_t *resolutions_host,
+                                                  const int32_t *codebook_first_idx, int64_t table_rows, const float *coords,
+                                                  const void *codebook, const void *grad_output,
+                                                  const float *grad_grad_coords, int dtype, void *grad_grad_output,
+                                                  void *grad_codebook, float *grad_coords, const void *plan,
+                                                  size_t plan_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Triplane sampling (ABI 11, additive): TriplanarGrid (reference wisp/models/grids/triplanar_grid.py). LOD l of a call has
  * three fp32 planes fmx, fmy, fmz, each the module's NCHW parameter [1, F, S_l, S_l], S_l = 2^lods_host[l] + 1, passed as a
  * HOST array of 3 * num_lods device pointers ordered [3 * l + p] (p = 0 fmx, 1 fmy, 2 fmz; copied into the kernel arguments,

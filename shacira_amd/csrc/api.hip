@@ -274,6 +274,50 @@ int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, int num_lods, 
                                              num_coords, (hipStream_t)stream, plan);
 }
 
+size_t shacira_hashgrid_coords_backward2_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
+                                                         int codebook_bitwidth, const int32_t *resolutions_host,
+                                                         int64_t table_rows, int dtype) {
+    LevelTable lt;
+    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
+    (void)num_coords;
+    // fp16 tables: the fp32 image grad_codebook is accumulated in (used only by calls that ask for grad_codebook)
+    return dtype == SHACIRA_F16 ? (size_t)table_rows * (size_t)feature_dim * sizeof(float) : 0;
+}
+
+int shacira_hashgrid_coords_backward2(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
+                                      const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
+                                      const float *coords, const void *codebook, const void *grad_output,
+                                      const float *grad_grad_coords, int dtype, void *grad_grad_output, void *grad_codebook,
+                                      float *grad_coords, const void *plan, size_t plan_bytes, void *workspace,
+                                      size_t workspace_bytes, void *stream) {
+    options_snapshot();
+    LevelTable lt;
+    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
+    if (rc) return rc;
+    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16) return SHACIRA_EDTYPE;   // (fp64 tables included: first order only)
+    if (num_coords < 0) return SHACIRA_EINVAL;
+    if (!grad_grad_output && !grad_codebook && !grad_coords) return SHACIRA_EINVAL;
+    if (num_coords > 0) {
+        if (!codebook_first_idx || !coords || !grad_grad_coords) return SHACIRA_EINVAL;
+        if (!codebook && (grad_grad_output || grad_coords)) return SHACIRA_EINVAL;
+        if (!grad_output && (grad_codebook || grad_coords)) return SHACIRA_EINVAL;
+        if (grad_codebook && dtype == SHACIRA_F16 && table_rows > 0) {
+            const size_t need = shacira_hashgrid_coords_backward2_workspace_bytes(
+                dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype);
+            if (!workspace || workspace_bytes < need) return SHACIRA_EWORKSPACE;
+        }
+        // the plan of a shape whose forward sorts nothing does not exist: such a buffer is ignored
+        if (plan != nullptr) {
+            const bool sorts = table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
+            if (!sorts) plan = nullptr;
+            else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
+        }
+    }
+    return (int)hashgrid_coord_grad2_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, grad_output,
+                                              grad_grad_coords, grad_grad_output, grad_codebook, grad_coords, workspace,
+                                              num_coords, (hipStream_t)stream, plan);
+}
+
 // ---- triplanes ---------------------------------------------------------------------------------------------------------
 static int triplane_args(int64_t num_coords, int num_lods, const int32_t *lods_host, int feature_dim, TriplaneArgs &a) {
     if (num_coords < 0 || num_coords > (int64_t)INT32_MAX) return SHACIRA_EINVAL;

@@ -4,47 +4,18 @@
 // (the contract and its evaluation order: include/shacira_hip.h above shacira_hashgrid_coords_backward). A gather with no
 // atomics: the corner rows of the forward plus one grad_output row per sample in, DIM floats per sample out. Every kernel
 // below evaluates the same expression tree (coord_level_sums + the level chain), so the result for a sample depends on that
-// sample alone and all variants agree bit for bit:
+// sample alone and all variants agree bit for bit (coord_feature_diffs: hashgrid_coord_terms.h):
 //   variant 0  lane = sample, every level in turn; any even F (runtime F), fp64 tables   [default: calls without a plan]
 //   variant 3  lane pair = sample: lane dx gathers the corners x + dx (one request for the x / x+1 pair, the forward's
 //              variant 3), the partner's values come over DPP  (measured slower than 0 on every shape: kept for A/B)
 //   variant 8  variant 3 over the sorted records of the batch's plan (the forward's rows kernel order: neighbouring samples
 //              share coarse-level lines in L1), results go to grad_coords[perm[i]]         [default: 3-D calls with a plan]
 // (option "coord_variant"; -1 = the rule above, measured in profiles/coord_grad.md. DESIGN.md 4.3a.)
+#include "hashgrid_coord_terms.h"
 #include "hashgrid_rows.h"
 #include "internal.h"
 
 namespace shacira {
-
-// One feature of one level: D[a] = sum over the corner pairs of axis a, k0 ascending, of W_a(k0) * (v[k1] - v[k0]), as
-// D = d0 * W0, then D = fmaf(d, W, D). W_a(k0) = the other axes' weights (f if the corner's bit is set, g otherwise) as a
-// left-to-right product in axis order. Corner k: bit DIM-1-a -> axis a (the forward's corner order).
-template <int DIM>
-__device__ __forceinline__ void coord_feature_diffs(const float (&f)[DIM], const float (&g)[DIM], const float (&v)[1 << DIM],
-                                                    float (&D)[DIM]) {
-    constexpr int NC = 1 << DIM;
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-        const int bit = 1 << (DIM - 1 - a);
-        bool first = true;
-#pragma unroll
-        for (int k0 = 0; k0 < NC; ++k0) {
-            if (k0 & bit) continue;
-            float w = 0.0f;
-            bool wfirst = true;
-#pragma unroll
-            for (int b = 0; b < DIM; ++b) {
-                if (b == a) continue;
-                const float wb = (k0 & (1 << (DIM - 1 - b))) ? f[b] : g[b];
-                w = wfirst ? wb : w * wb;
-                wfirst = false;
-            }
-            const float d = v[k0 | bit] - v[k0];
-            D[a] = first ? d * w : fmaf(d, w, D[a]);
-            first = false;
-        }
-    }
-}
 
 // One level, F features: S[a] = g0 * D0[a], then S[a] = fmaf(g_f, D_f[a], S[a]) for f ascending.
 template <int DIM, int F>

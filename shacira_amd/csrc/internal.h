@@ -65,6 +65,13 @@ hipError_t hashgrid_debug_corners(int dim, const LevelTable &lt, const float *co
 hipError_t hashgrid_coord_grad_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
                                         const float *coords, const void *table, const void *grad_out,
                                         float *grad_coords, int64_t n, hipStream_t s, const void *plan);
+// hashgrid_coord_grad2.hip: the backward of the call above for `vv` = dL/dgrad_coords [n, dim]; NULL outputs are not computed
+// (ggo [n, L * F] of the table's dtype, grad_table [table_rows, F] overwritten -- fp16: accumulated in `workspace` --,
+// grad_coords [n, dim] fp32)
+hipError_t hashgrid_coord_grad2_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
+                                         const float *coords, const void *table, const void *grad_out, const float *vv,
+                                         void *ggo, void *grad_table, float *grad_coords, void *workspace, int64_t n,
+                                         hipStream_t s, const void *plan);
 // hashgrid_bwd.hip
 hipError_t zero_fill_async(float *p, int64_t n, hipStream_t s);   // zero fill as a kernel (graph-capture safe)
 size_t hashgrid_backward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n);

@@ -327,6 +327,58 @@ def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_
     return grad_coords
 
 
+def hashgrid_coords_backward2(dim, coords, grad_output, grad_grad_coords, codebook, codebook_first_idx, resolution,
+                              codebook_bitwidth, want=(True, True, True), plan=None):
+    """Backward of ``hashgrid_coords_backward`` for ``grad_grad_coords`` = dL/dgrad_coords (fp32 [N, dim]): the tuple
+    (grad_grad_output [N, L*F] in the table's dtype, grad_codebook [T, F] in the table's dtype, grad_coords fp32 [N, dim]),
+    ``None`` where ``want`` is false (include/shacira_hip.h, shacira_hashgrid_coords_backward2). fp32 and fp16 tables."""
+    _check_float_coords(dim, coords, grad_output, grad_grad_coords, codebook, codebook_first_idx)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 3:
+        raise RuntimeError("want must have three entries: (grad_grad_output, grad_codebook, grad_coords)")
+    if not any(want):
+        return None, None, None
+    if codebook.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"shacira_amd: the second-order hash-grid gradients are implemented for fp32 and fp16 tables, "
+                           f"not {codebook.dtype}")
+    res = tuple(int(r) for r in resolution)
+    N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
+    dt = _dtype_code(codebook)
+    device = coords.device
+    codebook = codebook.contiguous()
+    if grad_output.dtype != codebook.dtype:
+        grad_output = grad_output.to(codebook.dtype)
+    grad_output = grad_output.contiguous()
+    if tuple(grad_output.shape) != (N, len(res) * F):
+        raise RuntimeError(f"grad_output must be [{N}, {len(res) * F}], got {tuple(grad_output.shape)}")
+    v = grad_grad_coords
+    if v.dtype != torch.float32:
+        v = v.float()
+    v = v.contiguous()
+    if tuple(v.shape) != (N, dim):
+        raise RuntimeError(f"grad_grad_coords must be [{N}, {dim}], got {tuple(v.shape)}")
+    ggo = torch.empty((N, len(res) * F), dtype=codebook.dtype, device=device) if want[0] else None
+    gcb = torch.empty((T, F), dtype=codebook.dtype, device=device) if want[1] else None
+    gc = torch.empty((N, dim), dtype=torch.float32, device=device) if want[2] else None
+    if N == 0 and (not want[1] or T == 0):     # nothing to compute, no table to zero
+        return ggo, gcb, gc
+    L = _lib.lib()
+    with _on_device(device):
+        nbytes = 0
+        if want[1]:
+            nbytes = int(L.shacira_hashgrid_coords_backward2_workspace_bytes(dim, N, len(res), F, int(codebook_bitwidth),
+                                                                              _res_array(res), T, dt))
+        ws = _workspace(device, nbytes)
+        if plan is not None:
+            _need_gpu(plan)
+        rc = L.shacira_hashgrid_coords_backward2(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
+                                                 _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook),
+                                                 _ptr(grad_output), _ptr(v), dt, _ptr(ggo), _ptr(gcb), _ptr(gc), _ptr(plan),
+                                                 0 if plan is None else plan.numel(), _ptr(ws), nbytes, _stream(coords))
+    _lib.check(rc, "hashgrid_coords_backward2")
+    return ggo, gcb, gc
+
+
 def hashgrid_debug_corners(dim, coords, resolution, codebook_bitwidth):
     """Test hook: (rows int32 [N, L, 2^dim], weights fp32 [N, L, 2^dim]) exactly as the kernels compute them."""
     _check_float_coords(dim, coords)
