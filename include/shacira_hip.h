@@ -396,6 +396,68 @@ SHACIRA_API int shacira_octree_backward(int64_t num_coords, int num_levels, cons
                                         size_t workspace_bytes, void *stream);
 
 /*
+ * Mesh to signed distance (ABI 11, additive): the reference's `mesh_to_sdf_cuda` (wisp/ops/mesh/compute_sdf.py; kernels
+ * kernel_mesh2sdf_quad + kernel_quad_aggr of wisp/csrc/external/mesh2sdf_kernel.cu): for every point the distance to the
+ * nearest non-degenerate triangle, negative where the point is inside by 13-direction ray stabbing. Brute force over the
+ * N x T pairs.
+ *
+ *   points     [N, 3] fp32
+ *   triangles  [T, 3, 3] fp32: the vertices a, b, c of every triangle (V[F])
+ *   sdf        out, [N] fp32
+ *
+ * All arithmetic is fp32, evaluated WITHOUT contraction (the library is built with -ffp-contract=off -fno-fast-math), in
+ * these fixed shapes:
+ *   dot(x, y)   = (x0*y0 + x1*y1) + x2*y2
+ *   cross(x, y) = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0)
+ *   |t|^2       = (t0*t0 + t1*t1) + t2*t2
+ *   sgn(x)      = copysignf(1, x);   clamp01(x) = fmaxf(0, fminf(x, 1));   reciprocals are IEEE 1.0f / x
+ * Per triangle:
+ *   e0 = b - a, e1 = c - b, e2 = a - c;  n = cross(e0, e2);  m_i = cross(e_i, n);  r_i = 1 / dot(e_i, e_i);
+ *   r_n = 1 / dot(n, n);  g = -e2
+ * Per (point p, triangle) pair:  p0 = p - a, p1 = p - b, p2 = p - c.
+ * Distance, only for triangles with a non-zero n (any component != 0):
+ *   s = (sgn(dot(m0, p0)) + sgn(dot(m1, p1))) + sgn(dot(m2, p2))
+ *   s < 2:      d2 = fminf(E0, fminf(E1, E2)),  E_i = |e_i * clamp01(dot(e_i, p_i) * r_i) - p_i|^2
+ *               (component-wise t_k = e_ik * x - p_ik)
+ *   otherwise:  d2 = (dot(n, p0) * dot(n, p0)) * r_n
+ *   a negative d2 becomes 0;  m = fminf of d2 over all such triangles, +inf if there are none.
+ * Ray stabbing, for EVERY triangle (degenerate ones included):
+ *   q = cross(p0, e0);  tau = dot(g, q)
+ *   the 13 directions, in this order, h = 0.707106781f, k = 0.577350269f:
+ *     (1,0,0) (0,1,0) (0,0,1)  (0,h,h) (h,0,h) (h,h,0)  (0,h,-h) (h,0,-h) (h,-h,0)  (k,k,k) (-k,k,k) (k,-k,k) (k,k,-k)
+ *   per direction dir:  w = cross(dir, g);  det = dot(e0, w);  skipped when -1e-8 < det < 1e-8 (det widened to double and
+ *     compared with the double constants: (float)1e-8 is a different threshold);  inv = 1 / det;
+ *     u = dot(p0, w) * inv, skipped if u < 0 or u > 1;   v = dot(dir, q) * inv, skipped if v < 0 or u + v > 1;
+ *     t = tau * inv:  t >= 0 sets pos[dir], otherwise neg[dir].
+ * Result:  dist = sqrtf(m);  the point is inside iff every one of the 13 directions has both pos and neg set;
+ *          sdf = inside ? -dist : dist.
+ * T == 0 gives +inf everywhere. Non-finite points or vertices do not fault; their outputs are unspecified.
+ *
+ * The minimum and the 26 flags are order-free and every other value is a function of one triangle or of one (point,
+ * triangle) pair: any partition of the triangles over lanes, workgroups or passes gives the same bits, and so does
+ * precomputing the per-triangle and per-(triangle, direction) quantities. (The kernels leave out the terms of dot(dir, q) whose
+ * direction component is a literal 0: for finite inputs that changes at most the sign of a zero, which no comparison above
+ * sees.) nvcc contracts by default, so the reference's own bits can differ in the last place; the contract is the uncontracted
+ * sequence, the position the hash-grid oracle's mode 0 takes.
+ *
+ *   workspace  shacira_mesh_sdf_workspace_bytes(N, T) bytes, 16-byte aligned: the per-triangle records of ONE pass (the
+ *              triangles are processed in passes of SHACIRA_MESH_SDF_PASS_TRIANGLES, so at most that many records of 352
+ *              bytes: 5.5 MiB whatever T) plus 8 bytes per point (minimum and flags, merged across triangle chunks with one
+ *              atomicMin and one atomicOr per point and chunk). 0 when N == 0 or T == 0 (workspace may then be NULL). The call
+ *              initialises everything it reads from it: stale contents do not matter. Within a pass a workgroup row walks
+ *              a chunk of triangles whose length is a multiple of SHACIRA_MESH_SDF_CHUNK_GRANULE; the number of chunks is
+ *              chosen from N and T (small N: enough chunks to fill the chip; large N: one).
+ * Bounds: 0 <= N, T < 2^31. Validation happens before any HIP call: negative or too large counts and NULL operands return
+ * SHACIRA_EINVAL, a workspace below the query SHACIRA_EWORKSPACE; N == 0 returns 0 and launches nothing; T == 0 fills +inf.
+ * Everything runs on `stream`; no host synchronisation and no allocation: safe to capture into a graph.
+ */
+#define SHACIRA_MESH_SDF_PASS_TRIANGLES 16384
+#define SHACIRA_MESH_SDF_CHUNK_GRANULE 32
+SHACIRA_API size_t shacira_mesh_sdf_workspace_bytes(int64_t num_points, int64_t num_triangles);
+SHACIRA_API int shacira_mesh_sdf(int64_t num_points, int64_t num_triangles, const float *points, const float *triangles,
+                                 float *sdf, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

@@ -17,6 +17,7 @@ BWD_STAGE_ALL_LEVELS, BWD_REUSE_STAGED = 1, 2
 PLAN_READY = 1
 TRIPLANE_GRAD_PLANES, TRIPLANE_GRAD_COORDS = 1, 2
 OCTREE_GRAD_FEATURES, OCTREE_GRAD_COORDS = 1, 2
+MESH_SDF_PASS_TRIANGLES, MESH_SDF_CHUNK_GRANULE = 16384, 32   # SHACIRA_MESH_SDF_* of the header
 
 _lock = threading.Lock()
 _lib = None
@@ -55,6 +56,8 @@ SIGNATURES = {
     "shacira_octree_forward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p]),
     "shacira_octree_backward_workspace_bytes": (_sz, [_i64, _i, _p, _i, _i, _i]),
     "shacira_octree_backward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "shacira_mesh_sdf_workspace_bytes": (_sz, [_i64, _i64]),
+    "shacira_mesh_sdf": (_i, [_i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "shacira_latent_decode_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),
     "shacira_latent_decode_backward_workspace_bytes": (_sz, [_i64, _i, _i]),
     "shacira_latent_decode_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),

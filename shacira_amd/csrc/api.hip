@@ -505,6 +505,26 @@ int shacira_octree_backward(int64_t num_coords, int num_levels, const int32_t *l
                                          want_coords ? grad_coords : nullptr, workspace, num_coords, (hipStream_t)stream);
 }
 
+// ---- mesh to signed distance -----------------------------------------------------------------------------------------------
+static bool mesh_counts_ok(int64_t num_points, int64_t num_triangles) {
+    return num_points >= 0 && num_triangles >= 0 && num_points <= INT32_MAX && num_triangles <= INT32_MAX;
+}
+
+size_t shacira_mesh_sdf_workspace_bytes(int64_t num_points, int64_t num_triangles) {
+    if (!mesh_counts_ok(num_points, num_triangles)) return 0;
+    return mesh_sdf_workspace(num_points, num_triangles);
+}
+
+int shacira_mesh_sdf(int64_t num_points, int64_t num_triangles, const float *points, const float *triangles, float *sdf,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (!mesh_counts_ok(num_points, num_triangles)) return SHACIRA_EINVAL;
+    if (num_points == 0) return 0;
+    if (!points || !sdf || (num_triangles > 0 && !triangles)) return SHACIRA_EINVAL;
+    const size_t need = mesh_sdf_workspace(num_points, num_triangles);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    return (int)mesh_sdf_dispatch(num_points, num_triangles, points, triangles, sdf, workspace, (hipStream_t)stream);
+}
+
 static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
                          const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
                          const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,

@@ -137,6 +137,11 @@ hipError_t octree_forward_dispatch(const OctreeArgs &a, const float *coords, int
 hipError_t octree_backward_dispatch(const OctreeArgs &a, const float *coords, const float *grad_out, int sum,
                                     bool features, float *grad_coords, void *workspace, int64_t n, hipStream_t s);
 
+// mesh_sdf.hip: signed distance of n points to t triangles (0 <= n, t < 2^31, checked by the entry point)
+size_t mesh_sdf_workspace(int64_t n, int64_t t);
+hipError_t mesh_sdf_dispatch(int64_t n, int64_t t, const float *points, const float *tris, float *sdf, void *workspace,
+                             hipStream_t s);
+
 // latent.hip
 struct DecodeArgs {
     const float *latent, *div, *matrix, *colscale, *shift;

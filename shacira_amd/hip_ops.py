@@ -937,3 +937,29 @@ def octree_backward(coords, levels, feature_dim, grad_output, multiscale_sum, fe
                                        nbytes, _stream(coords))
     _lib.check(rc, "octree_backward")
     return grads, grad_coords
+
+
+# ---- mesh to signed distance (include/shacira_hip.h, shacira_mesh_sdf) -------------------------------------------------------
+def mesh_sdf(points, triangles):
+    """Signed distance [N] fp32 of ``points`` [N, 3] to the triangles [T, 3, 3] (the vertices a, b, c of each: ``V[F]``),
+    negative inside by 13-direction ray stabbing: the reference's ``_C.external.mesh_to_sdf_cuda``. Operands that are not
+    contiguous fp32 are copied; ``triangles`` is moved to the device of ``points``. T == 0 gives +inf."""
+    _need_gpu(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"shacira_amd: points must be [N, 3], got {tuple(points.shape)}")
+    if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
+        raise RuntimeError(f"shacira_amd: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+    dev = points.device
+    points = points.detach().to(dtype=torch.float32).contiguous()
+    triangles = triangles.detach().to(device=dev, dtype=torch.float32).contiguous()
+    N, T = points.shape[0], triangles.shape[0]
+    sdf = torch.empty((N,), dtype=torch.float32, device=dev)
+    if N == 0:
+        return sdf
+    L = _lib.lib()
+    with _on_device(dev):
+        nbytes = int(L.shacira_mesh_sdf_workspace_bytes(N, T))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_mesh_sdf(N, T, _ptr(points), _ptr(triangles), _ptr(sdf), _ptr(ws), nbytes, _stream(points))
+    _lib.check(rc, "mesh_sdf")
+    return sdf
