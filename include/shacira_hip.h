@@ -769,6 +769,68 @@ SHACIRA_API int shacira_raytrace_dense_emit(int64_t num_rays, const float *origi
                                 int32_t *pidx, float *depth, void *stream);
 
 /*
+ * Sphere tracing over ray packs (ABI 11, additive): the reference's `find_depth_bound_cuda`
+ * (wisp/csrc/render/find_depth_bound_cuda.cu) and, as ONE launch per iteration, the body of the loop of its
+ * PackedSDFTracer.trace (wisp/tracers/packed_sdf_tracer.py), which runs there as about 25 masked element-wise launches, a
+ * boolean-index compaction and two mask.any() read-backs per iteration.
+ *
+ * Notation. The nuggets (ray, cell) of a trace are depth [K, 2] fp32 = (entry, exit), sorted by ray and then by depth, as
+ * shacira_raytrace_dense_emit writes them. A PACK is the nuggets of one ray: pack p is [first[p], end[p]) with
+ * end[p] = first[p + 1], and THE LAST PACK ENDS AT K. Callers pass end[] as pack_end int32 [P]. Indices are int32.
+ *
+ * find_depth_bound. For pack p with current nugget c = curr_idxes[p] and query depth q = query[p], out[p] is
+ *   -1                                   if c < 0;
+ *   the first i in [c, end[p]) with (q >= entry_i && q <= exit_i) || q < entry_i;
+ *   -1                                   if there is none. A NaN q satisfies neither comparison and gives -1.
+ * Every out[p] is written. This is the reference's rule with two of its defects removed:
+ *   (a) the reference bounds the walk of pack p by curr_idxes_in[p + 1], the neighbour's CURRENT nugget: once the neighbour
+ *       has advanced, the walk of p runs into the neighbour's nuggets. Here the bound is the pack's own end;
+ *   (b) for the last pack the reference bounds the walk by num_packs where num_nugs is meant, so the last ray can never
+ *       advance (its walk is empty whenever its current nugget is >= num_packs). Here the last pack ends at K.
+ * Where the reference stays inside its own pack the two rules agree: every pack but the last on the first call, when
+ * curr_idxes is the list of pack starts. (The reference also leaves out[p] unwritten where it finds nothing; its caller
+ * pre-fills -1.) The walk never reads past K: pack_end values above num_nugs are treated as num_nugs.
+ *
+ * Sphere-trace step. Per pack, fp32, one rounding per operator (no contraction: -ffp-contract=off, as for shacira_mesh_sdf).
+ * State, structure of arrays over the P packs: t, dist, dist_prev fp32 [P], curr int32 [P], x fp32 [P, 3], active and hit
+ * uint8 [P]; o = origins[p], d = dirs[p] are the pack's ray (fp32 [P, 3], gathered per pack by the caller).
+ *   Init (the caller's, once per trace):  curr = first[p];  t = entry[curr] (the caller has added 1e-5f to every entry
+ *     beforehand, as the reference does in place);  x = o + d * t;  active = 1;  hit = 0.
+ *   Iteration i = 0 .. num_steps - 1, for the ACTIVE packs only, given s = sdf(x) evaluated by the caller:
+ *     dist = s * step_size;  at i == 0 (first_iteration != 0) also dist_prev = dist
+ *     t = t + dist;  x = o + d * t                                  (component-wise: x_k = o_k + d_k * t)
+ *     hit = |dist| < min_dis  ||  |dist + dist_prev| * 0.5f < 5.0f * min_dis      (5.0f * min_dis rounded to fp32 once)
+ *     if hit or !(t < dist_max): the pack retires (active = 0) with its state frozen
+ *     otherwise dist_prev = dist and n = find_depth_bound(t, curr):
+ *       n == -1: the pack retires as a miss (active = 0, hit = 0)
+ *       else:    if n != curr then t = entry[n];  curr = n;  x = o + d * t;  the pack is appended to the next active list
+ *                with x (and pidx[curr] where pidx is given)
+ * A retired pack's t and x are never touched again, so x == o + d * t holds bitwise for every pack. This is a stated
+ * deviation: the reference's `t += dist` is unmasked, so a hit ray's reported depth keeps drifting by its last dist on every
+ * later iteration. hit and x are unaffected by it. A NaN or +inf sdf retires the pack without a hit (no comparison holds).
+ *
+ * shacira_sphere_trace_step does all of this in one launch for the num_active packs named by active_in [num_active]
+ * (slot j: pack active_in[j], its value sdf[j]); one lane per slot. Survivors are appended to active_out, coords_out
+ * [., 3] and (pidx != NULL) pidx_out wave by wave: one ballot and one atomic add to *count_out per wave, so the survivors of a
+ * wave stay in lane order. The order of whole waves in the next list is not fixed; a pack's results do not depend on the
+ * order of the list. No workgroup waits on another. *count_out must be 0 when the launch starts; the launch sets *count_next
+ * (a different int32: the counter of the FOLLOWING launch) to 0, so two counters used in turn need no clearing in between.
+ * num_active == 0 returns 0 and launches nothing.
+ * Bounds: 0 <= P, K < 2^31 (SHACIRA_EINVAL otherwise), P <= K (a pack holds at least one nugget), num_active <= P. NULL
+ * operands are refused (SHACIRA_EINVAL) before any HIP call; find_depth_bound with P == 0 returns 0 without a launch. Slots
+ * that name a pack outside [0, P) are ignored. Everything runs on `stream`; no host synchronisation and no allocation.
+ */
+SHACIRA_API int shacira_find_depth_bound(int64_t num_packs, int64_t num_nugs, const float *query, const int32_t *curr_idxes,
+                                         const int32_t *pack_end, const float *depth, int32_t *out, void *stream);
+SHACIRA_API int shacira_sphere_trace_step(int64_t num_packs, int64_t num_nugs, int64_t num_active, int first_iteration,
+                                          const int32_t *active_in, const float *sdf, const float *origins,
+                                          const float *dirs, const float *depth, const int32_t *pack_end,
+                                          const int32_t *pidx, float step_size, float min_dis, float dist_max, float *t,
+                                          float *dist, float *dist_prev, int32_t *curr, float *x, uint8_t *active,
+                                          uint8_t *hit, int32_t *active_out, float *coords_out, int32_t *pidx_out,
+                                          int32_t *count_out, int32_t *count_next, void *stream);
+
+/*
  * Diagnostics: one streaming pass over `bytes` (a multiple of 16; 16-byte aligned buffers) with the access shape of the
  * hash-grid kernels -- 16 bytes per lane, 8 in flight, non-temporal. kind 0 = read `src` (`dst` may be NULL or a 4-byte
  * scratch word), 1 = write `dst`, 2 = copy `src` -> `dst`. bench.py times it for `roofline.measured_stream_rates`.

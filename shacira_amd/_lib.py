@@ -58,6 +58,9 @@ SIGNATURES = {
     "shacira_octree_backward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "shacira_mesh_sdf_workspace_bytes": (_sz, [_i64, _i64]),
     "shacira_mesh_sdf": (_i, [_i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "shacira_find_depth_bound": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
+                                       _p, _p, _p, _p, _p, _p, _p]),
     "shacira_latent_decode_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),
     "shacira_latent_decode_backward_workspace_bytes": (_sz, [_i64, _i, _i]),
     "shacira_latent_decode_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -525,6 +525,38 @@ int shacira_mesh_sdf(int64_t num_points, int64_t num_triangles, const float *poi
     return (int)mesh_sdf_dispatch(num_points, num_triangles, points, triangles, sdf, workspace, (hipStream_t)stream);
 }
 
+// ---- sphere tracing over ray packs ---------------------------------------------------------------------------------------
+static bool trace_counts_ok(int64_t num_packs, int64_t num_nugs) {
+    return num_packs >= 0 && num_nugs >= 0 && num_packs <= INT32_MAX && num_nugs <= INT32_MAX && num_packs <= num_nugs;
+}
+
+int shacira_find_depth_bound(int64_t num_packs, int64_t num_nugs, const float *query, const int32_t *curr_idxes,
+                             const int32_t *pack_end, const float *depth, int32_t *out, void *stream) {
+    if (!trace_counts_ok(num_packs, num_nugs)) return SHACIRA_EINVAL;
+    if (num_packs == 0) return 0;
+    if (!query || !curr_idxes || !pack_end || !depth || !out) return SHACIRA_EINVAL;
+    return (int)find_depth_bound_launch(num_packs, num_nugs, query, curr_idxes, pack_end, depth, out, (hipStream_t)stream);
+}
+
+int shacira_sphere_trace_step(int64_t num_packs, int64_t num_nugs, int64_t num_active, int first_iteration,
+                              const int32_t *active_in, const float *sdf, const float *origins, const float *dirs,
+                              const float *depth, const int32_t *pack_end, const int32_t *pidx, float step_size,
+                              float min_dis, float dist_max, float *t, float *dist, float *dist_prev, int32_t *curr,
+                              float *x, uint8_t *active, uint8_t *hit, int32_t *active_out, float *coords_out,
+                              int32_t *pidx_out, int32_t *count_out, int32_t *count_next, void *stream) {
+    if (!trace_counts_ok(num_packs, num_nugs)) return SHACIRA_EINVAL;
+    if (num_active < 0 || num_active > num_packs) return SHACIRA_EINVAL;
+    if (num_active == 0) return 0;
+    if (!active_in || !sdf || !origins || !dirs || !depth || !pack_end || !t || !dist || !dist_prev || !curr || !x ||
+        !active || !hit || !active_out || !coords_out || !count_out || !count_next || count_out == count_next)
+        return SHACIRA_EINVAL;
+    if (pidx && !pidx_out) return SHACIRA_EINVAL;
+    return (int)sphere_trace_step_launch(num_packs, num_nugs, num_active, first_iteration != 0, active_in, sdf, origins,
+                                         dirs, depth, pack_end, pidx, step_size, min_dis, dist_max, t, dist, dist_prev,
+                                         curr, x, active, hit, active_out, coords_out, pidx_out, count_out, count_next,
+                                         (hipStream_t)stream);
+}
+
 static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
                          const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
                          const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,

@@ -142,6 +142,16 @@ size_t mesh_sdf_workspace(int64_t n, int64_t t);
 hipError_t mesh_sdf_dispatch(int64_t n, int64_t t, const float *points, const float *tris, float *sdf, void *workspace,
                              hipStream_t s);
 
+// sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
+hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
+                                   const float *depth, int32_t *out, hipStream_t s);
+hipError_t sphere_trace_step_launch(int64_t P, int64_t K, int64_t num_active, bool first, const int32_t *active_in,
+                                    const float *sdf, const float *origins, const float *dirs, const float *depth,
+                                    const int32_t *pack_end, const int32_t *pidx, float step_size, float min_dis,
+                                    float dist_max, float *t, float *dist, float *dist_prev, int32_t *curr, float *x,
+                                    uint8_t *active, uint8_t *hit, int32_t *active_out, float *coords_out,
+                                    int32_t *pidx_out, int32_t *count_out, int32_t *count_next, hipStream_t s);
+
 // latent.hip
 struct DecodeArgs {
     const float *latent, *div, *matrix, *colscale, *shift;

@@ -1,6 +1,6 @@
 """Sample generation on a dense occupancy grid and volume integration over ray packs (SURVEY.md section 8 "next" f2):
 tensor wrappers + autograd Functions over libshacira_hip.so's `shacira_pack_*`, `shacira_raymarch_ray_*`,
-`shacira_raytrace_dense_*`.
+`shacira_raytrace_dense_*`, and the sphere tracer's `shacira_find_depth_bound` / `shacira_sphere_trace_step`.
 
 Function names and argument order follow what the reference calls in kaolin 0.13 (`kaolin.render.spc` imported as
 ``spc_render`` in wisp/tracers/packed_rf_tracer.py:131-151 and wisp/accelstructs/octree_as.py:163-289), so the tracer
@@ -199,3 +199,84 @@ def raytrace_dense(origins, dirs, occupancy, level):
                                                  _ptr(ridx), _ptr(pidx), _ptr(depth), _stream(origins)),
                    "shacira_raytrace_dense_emit")
     return ridx, pidx, depth
+
+
+def find_depth_bound(query, curr_idxes, pack_end, depth):
+    """Per pack, the first nugget at or after ``curr_idxes[p]`` and before ``pack_end[p]`` that holds the depth ``query[p]``
+    or lies behind it, -1 if there is none or ``curr_idxes[p] < 0`` (the contract above ``shacira_find_depth_bound``).
+    query fp32 [P] or [P, 1], curr_idxes / pack_end int32 [P], depth fp32 [K, 2] -> int32 [P]."""
+    _need_gpu(query, curr_idxes, pack_end, depth)
+    query = query.float().contiguous().reshape(-1)
+    curr_idxes, pack_end = curr_idxes.int().contiguous(), pack_end.int().contiguous()
+    depth = depth.float().contiguous()
+    P, K = query.shape[0], depth.shape[0]
+    if curr_idxes.shape[0] != P or pack_end.shape[0] != P or depth.dim() != 2 or depth.shape[1] != 2:
+        raise RuntimeError("find_depth_bound: query, curr_idxes and pack_end must have one entry per pack, depth must be [K, 2]")
+    out = torch.empty((P,), dtype=torch.int32, device=query.device)
+    with _on_device(query.device):
+        _lib.check(_lib.lib().shacira_find_depth_bound(P, K, _ptr(query), _ptr(curr_idxes), _ptr(pack_end), _ptr(depth),
+                                                       _ptr(out), _stream(query)), "shacira_find_depth_bound")
+    return out
+
+
+class SphereTrace:
+    """The state of one sphere trace over P ray packs and its fused step (the contract above ``shacira_find_depth_bound``).
+
+    ``origins`` / ``dirs`` fp32 [P, 3] are the packs' rays, ``depth`` fp32 [K, 2] the nuggets (entries already offset by the
+    caller), ``first`` / ``pack_end`` int32 [P] each pack's first nugget and end, ``pidx`` int32 [K] optional. After the
+    constructor ``coords[:count]`` (and ``pidx_active[:count]``) are the positions to evaluate the field at, slot j belonging
+    to pack ``active_list[j]``; ``step(sdf)`` consumes those values in one launch, refills the three and returns the new count
+    (ONE device-to-host read-back). ``t, dist, dist_prev, curr, x, active, hit`` are the per-pack state."""
+
+    def __init__(self, origins, dirs, depth, first, pack_end, pidx=None, step_size=1.0, min_dis=0.0003,
+                 dist_max=float("inf")):
+        _need_gpu(origins, dirs, depth, first, pack_end, pidx)
+        dev = origins.device
+        self.origins, self.dirs = origins.float().contiguous(), dirs.float().contiguous()
+        self.depth = depth.float().contiguous()
+        self.pack_end = pack_end.int().contiguous()
+        self.pidx = pidx.int().contiguous() if pidx is not None else None
+        self.step_size, self.min_dis, self.dist_max = float(step_size), float(min_dis), float(dist_max)
+        P, K = self.origins.shape[0], self.depth.shape[0]
+        if tuple(self.origins.shape) != (P, 3) or tuple(self.dirs.shape) != (P, 3) or tuple(self.depth.shape) != (K, 2) \
+                or first.shape[0] != P or self.pack_end.shape[0] != P or (pidx is not None and pidx.shape[0] != K):
+            raise RuntimeError("SphereTrace: origins / dirs [P, 3], first / pack_end [P], depth [K, 2], pidx [K]")
+        self.num_packs, self.num_nugs = P, K
+        self.curr = first.int().clone().contiguous()
+        self.t = self.depth[:, 0].index_select(0, self.curr.long()).contiguous()
+        self.x = (self.origins + self.dirs * self.t[:, None]).contiguous()
+        self.dist = torch.zeros(P, dtype=torch.float32, device=dev)
+        self.dist_prev = torch.zeros(P, dtype=torch.float32, device=dev)
+        self.active = torch.ones(P, dtype=torch.uint8, device=dev)
+        self.hit = torch.zeros(P, dtype=torch.uint8, device=dev)
+        self.iteration = 0
+        self.count = P
+        self.active_list = torch.arange(P, dtype=torch.int32, device=dev)
+        self.coords = self.x.clone()
+        self.pidx_active = self.pidx.index_select(0, self.curr.long()) if self.pidx is not None else None
+        self._spare = (torch.empty_like(self.active_list), torch.empty_like(self.coords),
+                       torch.empty_like(self.pidx_active) if self.pidx is not None else None)
+        self._counters = torch.zeros(2, dtype=torch.int32, device=dev)   # used in turn: each launch clears the other one
+
+    def step(self, sdf):
+        """Consume ``sdf`` (one value per slot of the current active list); returns the number of survivors."""
+        if self.count == 0:
+            return 0
+        _need_gpu(sdf)
+        sdf = sdf.detach().float().contiguous().reshape(-1)
+        if sdf.shape[0] != self.count:
+            raise RuntimeError(f"SphereTrace.step: {self.count} active packs, {sdf.shape[0]} sdf values")
+        out_list, out_coords, out_pidx = self._spare
+        mine, other = self._counters[self.iteration & 1:], self._counters[(self.iteration + 1) & 1:]
+        with _on_device(sdf.device):
+            _lib.check(_lib.lib().shacira_sphere_trace_step(
+                self.num_packs, self.num_nugs, self.count, 1 if self.iteration == 0 else 0, _ptr(self.active_list),
+                _ptr(sdf), _ptr(self.origins), _ptr(self.dirs), _ptr(self.depth), _ptr(self.pack_end), _ptr(self.pidx),
+                self.step_size, self.min_dis, self.dist_max, _ptr(self.t), _ptr(self.dist), _ptr(self.dist_prev),
+                _ptr(self.curr), _ptr(self.x), _ptr(self.active), _ptr(self.hit), _ptr(out_list), _ptr(out_coords),
+                _ptr(out_pidx), _ptr(mine), _ptr(other), _stream(sdf)), "shacira_sphere_trace_step")
+        self._spare = (self.active_list, self.coords, self.pidx_active)
+        self.active_list, self.coords, self.pidx_active = out_list, out_coords, out_pidx
+        self.iteration += 1
+        self.count = int(self._counters[(self.iteration - 1) & 1].item())
+        return self.count

@@ -9,14 +9,15 @@ import importlib
 import sys
 
 _ALIASES = [
-    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.image", "ops.image.metrics", "core", "accelstructs", "accelstructs.aabb_as",
+    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.geometric", "ops.differential", "ops.image", "ops.image.metrics", "core", "accelstructs", "accelstructs.aabb_as",
     "models", "models.grids", "models.grids.blas_grid", "models.grids.hash_grid", "models.grids.latent_grid",
     "models.grids.triplanar_grid", "models.grids.octree_grid",
     "models.grids.codebook_grid", "models.latent_decoders",
     "models.latent_decoders.basic_latent_decoder", "models.latent_decoders.hierarchical_latent_decoder",
     "models.latent_decoders.multi_latent_decoder",
     "models.prob_models", "models.prob_models.bit_estimator", "models.decoders", "models.decoders.basic_decoders",
-    "models.embedders", "models.nefs", "models.nefs.nerf", "tracers", "tracers.packed_rf_tracer", "utils", "utils.schedulers",
+    "models.embedders", "models.nefs", "models.nefs.nerf", "models.nefs.neural_sdf", "tracers", "tracers.packed_rf_tracer",
+    "tracers.packed_sdf_tracer", "utils", "utils.schedulers",
 ]
 
 

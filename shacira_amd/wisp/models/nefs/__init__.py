@@ -1,3 +1,4 @@
 from .nerf import NeuralRadianceField
+from .neural_sdf import NeuralSDF
 
-__all__ = ["NeuralRadianceField"]
+__all__ = ["NeuralRadianceField", "NeuralSDF"]

@@ -4,19 +4,13 @@
 rule. The grid lookup runs through the HIP operators; the decoders use the fused MLP kernel when their shape is one of
 its instantiations and torch Linear layers otherwise.
 """
-import numpy as np
 import torch
 import torch.nn as nn
 
+from ...ops.geometric import sample_unif_sphere
 from ..decoders.basic_decoders import BasicDecoder
 from ..embedders import get_positional_embedder
 from ..grids import HashGrid, LatentGrid
-
-
-def sample_unif_sphere(n):
-    """n unit vectors, uniform on the sphere (normalised Gaussians, reference wisp/ops/geometric `sample_unif_sphere`)."""
-    u = np.random.randn(n, 3)
-    return u / np.linalg.norm(u, axis=1, keepdims=True)
 
 
 class NeuralRadianceField(nn.Module):
