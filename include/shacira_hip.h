@@ -458,6 +458,50 @@ SHACIRA_API int shacira_mesh_sdf(int64_t num_points, int64_t num_triangles, cons
                                  float *sdf, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Closest point on a mesh (ABI 11, additive): shacira_mesh_sdf keeping the winner. One pass over the N x T pairs gives the
+ * distance, the closest point and the index of the triangle it lies on (the reference's wisp/ops/mesh/closest_point.py is an
+ * `assert False`; closest_tex.py builds on it).
+ *
+ *   points     [N, 3] fp32
+ *   triangles  [T, 3, 3] fp32
+ *   flags      SHACIRA_MESH_CLOSEST_SIGNED: dist is negative inside (13-direction ray stabbing); any other bit: SHACIRA_EINVAL
+ *   dist       out, [N] fp32
+ *   hit        out, [N, 3] fp32: the closest point
+ *   tidx       out, [N] int32: the triangle it lies on, -1 if there is none
+ *
+ * Symbols, shapes and rounding are those of the shacira_mesh_sdf contract above. Per pair, d2 is exactly its d2 (a negative
+ * d2 becomes +0); only triangles with a non-zero n are candidates.
+ * Winner:  the candidate with the least d2; among equal d2 the lowest triangle index, counted over the whole mesh. A NaN d2
+ *          never wins (and neither does +inf): walking ascending indices from best = +inf, "replace iff d2 < best".
+ * dist:    sqrtf(d2 of the winner); with SIGNED negated where all 13 directions have both stab flags set, by the rule above.
+ *          So dist has the bits of shacira_mesh_sdf's sdf when SIGNED and of its absolute value otherwise. Without SIGNED
+ *          the stabbing is not executed at all.
+ * hit:     once per point, from the winning triangle:
+ *            s, x_i = clamp01(dot(e_i, p_i) * r_i) and E_i as above
+ *            s >= 2:     k = dot(n, p0) * r_n;  hit_j = p_j - n_j * k
+ *            otherwise:  i* = 0 if E0 <= E1 && E0 <= E2, else 1 if E1 <= E2, else 2;
+ *                        hit_j = v_{i*,j} + e_{i*,j} * x_{i*}   with v_0 = a, v_1 = b, v_2 = c
+ * No candidate (T == 0, or every triangle degenerate):  dist = +inf, tidx = -1, hit = p.
+ *
+ * The argmin with its tie rule, the minimum and the 26 flags are order-free and every other value is a function of one
+ * triangle or of one (point, triangle) pair: any partition of the triangles over lanes, chunks or passes gives the same bits.
+ * (Chunks are merged with one 64-bit atomicMin per point and chunk on (bits(d2) << 32) | index: non-negative floats order
+ * like their bits, and the low word is the tie rule.)
+ *
+ *   workspace  shacira_mesh_closest_workspace_bytes(N, T, flags) bytes, 16-byte aligned: the records of one pass, as for
+ *              shacira_mesh_sdf, plus 16 bytes per point (key, flags). 0 when N == 0 or the arguments are invalid. The call
+ *              initialises everything it reads from it.
+ * Bounds and validation as for shacira_mesh_sdf: 0 <= N, T < 2^31; negative or too large counts, unknown flag bits and NULL
+ * operands return SHACIRA_EINVAL and a workspace below the query SHACIRA_EWORKSPACE, all before any HIP call; N == 0 returns
+ * 0 and launches nothing. Everything runs on `stream`; no host synchronisation and no allocation: safe to capture.
+ */
+#define SHACIRA_MESH_CLOSEST_SIGNED 1
+SHACIRA_API size_t shacira_mesh_closest_workspace_bytes(int64_t num_points, int64_t num_triangles, int32_t flags);
+SHACIRA_API int shacira_mesh_closest(int64_t num_points, int64_t num_triangles, const float *points, const float *triangles,
+                                     int32_t flags, float *dist, float *hit, int32_t *tidx, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

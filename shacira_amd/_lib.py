@@ -18,6 +18,7 @@ PLAN_READY = 1
 TRIPLANE_GRAD_PLANES, TRIPLANE_GRAD_COORDS = 1, 2
 OCTREE_GRAD_FEATURES, OCTREE_GRAD_COORDS = 1, 2
 MESH_SDF_PASS_TRIANGLES, MESH_SDF_CHUNK_GRANULE = 16384, 32   # SHACIRA_MESH_SDF_* of the header
+MESH_CLOSEST_SIGNED = 1
 
 _lock = threading.Lock()
 _lib = None
@@ -58,6 +59,8 @@ SIGNATURES = {
     "shacira_octree_backward": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "shacira_mesh_sdf_workspace_bytes": (_sz, [_i64, _i64]),
     "shacira_mesh_sdf": (_i, [_i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "shacira_mesh_closest_workspace_bytes": (_sz, [_i64, _i64, ctypes.c_int32]),
+    "shacira_mesh_closest": (_i, [_i64, _i64, _p, _p, ctypes.c_int32, _p, _p, _p, _p, _sz, _p]),
     "shacira_find_depth_bound": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),

@@ -525,6 +525,23 @@ int shacira_mesh_sdf(int64_t num_points, int64_t num_triangles, const float *poi
     return (int)mesh_sdf_dispatch(num_points, num_triangles, points, triangles, sdf, workspace, (hipStream_t)stream);
 }
 
+size_t shacira_mesh_closest_workspace_bytes(int64_t num_points, int64_t num_triangles, int32_t flags) {
+    if (!mesh_counts_ok(num_points, num_triangles) || (flags & ~SHACIRA_MESH_CLOSEST_SIGNED)) return 0;
+    return mesh_closest_workspace(num_points, num_triangles);
+}
+
+int shacira_mesh_closest(int64_t num_points, int64_t num_triangles, const float *points, const float *triangles,
+                         int32_t flags, float *dist, float *hit, int32_t *tidx, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+    if (!mesh_counts_ok(num_points, num_triangles) || (flags & ~SHACIRA_MESH_CLOSEST_SIGNED)) return SHACIRA_EINVAL;
+    if (num_points == 0) return 0;
+    if (!points || !dist || !hit || !tidx || (num_triangles > 0 && !triangles)) return SHACIRA_EINVAL;
+    const size_t need = mesh_closest_workspace(num_points, num_triangles);
+    if (!workspace || workspace_bytes < need) return SHACIRA_EWORKSPACE;
+    return (int)mesh_closest_dispatch(num_points, num_triangles, points, triangles, (flags & SHACIRA_MESH_CLOSEST_SIGNED) != 0,
+                                      dist, hit, tidx, workspace, (hipStream_t)stream);
+}
+
 // ---- sphere tracing over ray packs ---------------------------------------------------------------------------------------
 static bool trace_counts_ok(int64_t num_packs, int64_t num_nugs) {
     return num_packs >= 0 && num_nugs >= 0 && num_packs <= INT32_MAX && num_nugs <= INT32_MAX && num_packs <= num_nugs;

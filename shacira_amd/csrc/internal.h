@@ -141,6 +141,10 @@ hipError_t octree_backward_dispatch(const OctreeArgs &a, const float *coords, co
 size_t mesh_sdf_workspace(int64_t n, int64_t t);
 hipError_t mesh_sdf_dispatch(int64_t n, int64_t t, const float *points, const float *tris, float *sdf, void *workspace,
                              hipStream_t s);
+// the same with the winner: distance, closest point and triangle index (flags validated by the entry point)
+size_t mesh_closest_workspace(int64_t n, int64_t t);
+hipError_t mesh_closest_dispatch(int64_t n, int64_t t, const float *points, const float *tris, bool is_signed, float *dist,
+                                 float *hit, int32_t *tidx, void *workspace, hipStream_t s);
 
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,

@@ -15,6 +15,10 @@
 //              like their bits) and one atomicOr of the flags into 8 bytes per point, initialised by the call; a last kernel
 //              takes the square root and applies the sign. A call with a single chunk finishes inside the pair kernel.
 //
+// shacira_mesh_closest (further down) is the same pair loop keeping the winning triangle as well: one compare and two selects
+// more per pair, a 64-bit atomicMin on (bits(d2), index) to combine, and a finish kernel that derives the closest point from
+// the winner. Templated on SIGNED: the unsigned instantiation carries no stab code.
+//
 // -DMESH_SDF_PLAIN=1 (make variant) builds the comparison kernel instead: one lane per point, no prologue, every
 // per-triangle quantity recomputed per pair from the vertices in global memory -- the shape of the reference's kernel. Same
 // bits; tools/mesh_sdf_ab.py times one against the other.
@@ -144,29 +148,30 @@ struct StabInput {
     float p0[3], q[3], tau;
 };
 
-// the distance part of one (point, triangle) pair, and the pair's q = cross(p0, e0), tau = dot(g, q) with g = -e2
-__device__ __forceinline__ void pair_distance(const TriRecord &r, PointState &s, StabInput &in) {
-    const float p00 = s.p[0] - r.a[0], p01 = s.p[1] - r.a[1], p02 = s.p[2] - r.a[2];
-    if (r.valid) {
-        const float p10 = s.p[0] - r.b[0], p11 = s.p[1] - r.b[1], p12 = s.p[2] - r.b[2];
-        const float p20 = s.p[0] - r.c[0], p21 = s.p[1] - r.c[1], p22 = s.p[2] - r.c[2];
-        const float sum = (sgn(dot3(r.m0[0], r.m0[1], r.m0[2], p00, p01, p02)) +
-                           sgn(dot3(r.m1[0], r.m1[1], r.m1[2], p10, p11, p12))) +
-                          sgn(dot3(r.m2[0], r.m2[1], r.m2[2], p20, p21, p22));
-        float d2;
-        if (sum < 2.f) {
-            const float x0 = clamp01(dot3(r.e0[0], r.e0[1], r.e0[2], p00, p01, p02) * r.r0);
-            const float x1 = clamp01(dot3(r.e1[0], r.e1[1], r.e1[2], p10, p11, p12) * r.r1);
-            const float x2 = clamp01(dot3(r.e2[0], r.e2[1], r.e2[2], p20, p21, p22) * r.r2);
-            d2 = fminf(edge_d2(r.e0, x0, p00, p01, p02),
-                       fminf(edge_d2(r.e1, x1, p10, p11, p12), edge_d2(r.e2, x2, p20, p21, p22)));
-        } else {
-            const float h = dot3(r.n[0], r.n[1], r.n[2], p00, p01, p02);
-            d2 = (h * h) * r.rn;
-        }
-        if (d2 < 0.f) d2 = 0.f;
-        s.m = fminf(s.m, d2);
+// d2 of one (point, triangle) pair for a triangle with a non-zero n; p0 = p - a
+__device__ __forceinline__ float pair_d2(const TriRecord &r, const float (&p)[3], float p00, float p01, float p02) {
+    const float p10 = p[0] - r.b[0], p11 = p[1] - r.b[1], p12 = p[2] - r.b[2];
+    const float p20 = p[0] - r.c[0], p21 = p[1] - r.c[1], p22 = p[2] - r.c[2];
+    const float sum = (sgn(dot3(r.m0[0], r.m0[1], r.m0[2], p00, p01, p02)) +
+                       sgn(dot3(r.m1[0], r.m1[1], r.m1[2], p10, p11, p12))) +
+                      sgn(dot3(r.m2[0], r.m2[1], r.m2[2], p20, p21, p22));
+    float d2;
+    if (sum < 2.f) {
+        const float x0 = clamp01(dot3(r.e0[0], r.e0[1], r.e0[2], p00, p01, p02) * r.r0);
+        const float x1 = clamp01(dot3(r.e1[0], r.e1[1], r.e1[2], p10, p11, p12) * r.r1);
+        const float x2 = clamp01(dot3(r.e2[0], r.e2[1], r.e2[2], p20, p21, p22) * r.r2);
+        d2 = fminf(edge_d2(r.e0, x0, p00, p01, p02),
+                   fminf(edge_d2(r.e1, x1, p10, p11, p12), edge_d2(r.e2, x2, p20, p21, p22)));
+    } else {
+        const float h = dot3(r.n[0], r.n[1], r.n[2], p00, p01, p02);
+        d2 = (h * h) * r.rn;
     }
+    if (d2 < 0.f) d2 = 0.f;
+    return d2;
+}
+
+// the pair's q = cross(p0, e0), tau = dot(g, q) with g = -e2
+__device__ __forceinline__ void stab_input(const TriRecord &r, float p00, float p01, float p02, StabInput &in) {
     in.p0[0] = p00;
     in.p0[1] = p01;
     in.p0[2] = p02;
@@ -174,6 +179,13 @@ __device__ __forceinline__ void pair_distance(const TriRecord &r, PointState &s,
     in.q[1] = p02 * r.e0[0] - p00 * r.e0[2];
     in.q[2] = p00 * r.e0[1] - p01 * r.e0[0];
     in.tau = dot3(-r.e2[0], -r.e2[1], -r.e2[2], in.q[0], in.q[1], in.q[2]);
+}
+
+// the distance part of one (point, triangle) pair, and what its 13 directions share
+__device__ __forceinline__ void pair_distance(const TriRecord &r, PointState &s, StabInput &in) {
+    const float p00 = s.p[0] - r.a[0], p01 = s.p[1] - r.a[1], p02 = s.p[2] - r.a[2];
+    if (r.valid) s.m = fminf(s.m, pair_d2(r, s.p, p00, p01, p02));
+    stab_input(r, p00, p01, p02, in);
 }
 
 template <int I> __device__ __forceinline__ void stab(const TriRecord &r, const StabInput &in, uint32_t &flags) {
@@ -187,13 +199,13 @@ template <int I> __device__ __forceinline__ void stab(const TriRecord &r, const 
 }
 
 // direction I for the P points of a lane: the skip bit is wave-uniform, one scalar branch around the whole direction
-template <int I, int P> __device__ __forceinline__ void stab_all(const TriRecord &r, const StabInput (&in)[P],
-                                                                 PointState (&s)[P]) {
+template <int I, int P, class S> __device__ __forceinline__ void stab_all(const TriRecord &r, const StabInput (&in)[P],
+                                                                          S (&s)[P]) {
     if (!((r.skip >> I) & 1u)) {
 #pragma unroll
         for (int j = 0; j < P; ++j) stab<I>(r, in[j], s[j].flags);
     }
-    if constexpr (I + 1 < 13) stab_all<I + 1, P>(r, in, s);
+    if constexpr (I + 1 < 13) stab_all<I + 1, P, S>(r, in, s);
 }
 
 // triangle r against the P points of a lane
@@ -201,7 +213,7 @@ template <int P> __device__ __forceinline__ void pair_update(const TriRecord &r,
     StabInput in[P];
 #pragma unroll
     for (int j = 0; j < P; ++j) pair_distance(r, s[j], in[j]);
-    stab_all<0, P>(r, in, s);
+    stab_all<0, P, PointState>(r, in, s);
 }
 
 __device__ __forceinline__ float finish(float m, uint32_t flags) {
@@ -217,6 +229,15 @@ __global__ void __launch_bounds__(kMeshBlock) mesh_sdf_fill_kernel(float *__rest
     else sdf[i] = INFINITY;
 }
 
+__global__ void __launch_bounds__(kMeshBlock) mesh_sdf_prologue_kernel(const float *__restrict__ tris,
+                                                                       TriRecord *__restrict__ rec, int32_t count) {
+    const int32_t t = (int32_t)(blockIdx.x * kMeshBlock + threadIdx.x);
+    if (t >= count) return;
+    TriRecord r;
+    tri_setup(tris + (size_t)t * 9, r);
+    rec[t] = r;
+}
+
 #if !MESH_SDF_PLAIN
 
 __global__ void __launch_bounds__(kMeshBlock) mesh_sdf_finish_kernel(const uint2 *__restrict__ acc, float *__restrict__ sdf,
@@ -225,15 +246,6 @@ __global__ void __launch_bounds__(kMeshBlock) mesh_sdf_finish_kernel(const uint2
     if (i >= n) return;
     const uint2 a = acc[i];
     sdf[i] = finish(__uint_as_float(a.x), a.y);
-}
-
-__global__ void __launch_bounds__(kMeshBlock) mesh_sdf_prologue_kernel(const float *__restrict__ tris,
-                                                                       TriRecord *__restrict__ rec, int32_t count) {
-    const int32_t t = (int32_t)(blockIdx.x * kMeshBlock + threadIdx.x);
-    if (t >= count) return;
-    TriRecord r;
-    tri_setup(tris + (size_t)t * 9, r);
-    rec[t] = r;
 }
 
 // rec: the records of this pass (count of them); blockIdx.y = chunk, triangles [chunk * chunk_len, +chunk_len) of the pass.
@@ -298,9 +310,130 @@ __global__ void __launch_bounds__(kMeshBlock) mesh_sdf_plain_kernel(const float 
 
 #endif
 
+// ---- closest point (shacira_mesh_closest): the same pair loop keeping the winner ----------------------------------------------
+// Per point 16 bytes of workspace: the key (bits(d2) << 32) | triangle index, merged with ONE 64-bit atomicMin per (point,
+// chunk) -- non-negative floats order like their bits and the low word breaks ties towards the lowest mesh-wide index -- and
+// the 26 stab flags (SIGNED only). The finish kernel reads the one winning triangle back and derives dist, hit, tidx from it.
+struct ClosestState {
+    float p[3];
+    float m;          // least d^2 so far: replaced iff d2 < m, so a NaN never wins and the first of equals stays
+    int32_t idx;      // its index within the pass, -1: none
+    uint32_t flags;
+};
+
+constexpr uint32_t kNoTriangle = 0xffffffffu;
+
+__global__ void __launch_bounds__(kMeshBlock) mesh_closest_fill_kernel(uint4 *__restrict__ acc, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    if (i < n) acc[i] = make_uint4(kNoTriangle, kInfBits, 0u, 0u);   // key = (+inf, -1), flags = 0
+}
+
+template <bool SIGNED, int P>
+__device__ __forceinline__ void closest_update(const TriRecord &r, int32_t t, ClosestState (&s)[P]) {
+    [[maybe_unused]] StabInput in[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const float p00 = s[j].p[0] - r.a[0], p01 = s[j].p[1] - r.a[1], p02 = s[j].p[2] - r.a[2];
+        if (r.valid) {
+            const float d2 = pair_d2(r, s[j].p, p00, p01, p02);
+            const bool better = d2 < s[j].m;
+            s[j].m = better ? d2 : s[j].m;
+            s[j].idx = better ? t : s[j].idx;
+        }
+        if constexpr (SIGNED) stab_input(r, p00, p01, p02, in[j]);
+    }
+    if constexpr (SIGNED) stab_all<0, P, ClosestState>(r, in, s);
+}
+
+// as mesh_sdf_pair_kernel; `first` is the mesh-wide index of the pass's first triangle
+template <bool SIGNED>
+__global__ void __launch_bounds__(kMeshBlock) mesh_closest_pair_kernel(const float *__restrict__ points,
+                                                                       const TriRecord *__restrict__ rec, int32_t count,
+                                                                       int32_t chunk_len, int32_t first,
+                                                                       uint4 *__restrict__ acc, int64_t n) {
+    const int64_t base = (int64_t)blockIdx.x * kMeshPointsPerBlock + threadIdx.x;
+    ClosestState s[kMeshPPL];
+#pragma unroll
+    for (int j = 0; j < kMeshPPL; ++j) {
+        const int64_t i = base + (int64_t)j * kMeshBlock;
+        const int64_t ld = i < n ? i : n - 1;        // idle lanes repeat the last point and store nothing
+        s[j].p[0] = points[ld * 3 + 0];
+        s[j].p[1] = points[ld * 3 + 1];
+        s[j].p[2] = points[ld * 3 + 2];
+        s[j].m = INFINITY;
+        s[j].idx = -1;
+        s[j].flags = 0u;
+    }
+    const int32_t t0 = (int32_t)blockIdx.y * chunk_len;
+    const int32_t t1 = min(t0 + chunk_len, count);
+    for (int32_t t = t0; t < t1; ++t) {
+        const TriRecord &r = rec[t];
+        closest_update<SIGNED, kMeshPPL>(r, t, s);
+    }
+#pragma unroll
+    for (int j = 0; j < kMeshPPL; ++j) {
+        const int64_t i = base + (int64_t)j * kMeshBlock;
+        if (i >= n) continue;
+        if (s[j].idx >= 0) {
+            const unsigned long long key =
+                ((unsigned long long)__float_as_uint(s[j].m) << 32) | (uint32_t)(first + s[j].idx);
+            atomicMin(reinterpret_cast<unsigned long long *>(acc + i), key);
+        }
+        if (SIGNED && s[j].flags) atomicOr(reinterpret_cast<uint32_t *>(acc + i) + 2, s[j].flags);
+    }
+}
+
+template <bool SIGNED>
+__global__ void __launch_bounds__(kMeshBlock) mesh_closest_finish_kernel(const float *__restrict__ points,
+                                                                         const float *__restrict__ tris,
+                                                                         const uint4 *__restrict__ acc,
+                                                                         float *__restrict__ dist, float *__restrict__ hit,
+                                                                         int32_t *__restrict__ tidx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint4 a = acc[i];
+    const float p[3] = {points[i * 3 + 0], points[i * 3 + 1], points[i * 3 + 2]};
+    float h[3] = {p[0], p[1], p[2]};
+    if (a.x != kNoTriangle) {
+        TriRecord r;
+        tri_setup(tris + (size_t)a.x * 9, r);
+        const float p0[3] = {p[0] - r.a[0], p[1] - r.a[1], p[2] - r.a[2]};
+        const float p1[3] = {p[0] - r.b[0], p[1] - r.b[1], p[2] - r.b[2]};
+        const float p2[3] = {p[0] - r.c[0], p[1] - r.c[1], p[2] - r.c[2]};
+        const float sum = (sgn(dot3(r.m0[0], r.m0[1], r.m0[2], p0[0], p0[1], p0[2])) +
+                           sgn(dot3(r.m1[0], r.m1[1], r.m1[2], p1[0], p1[1], p1[2]))) +
+                          sgn(dot3(r.m2[0], r.m2[1], r.m2[2], p2[0], p2[1], p2[2]));
+        if (sum >= 2.f) {
+            const float k = dot3(r.n[0], r.n[1], r.n[2], p0[0], p0[1], p0[2]) * r.rn;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) h[j] = p[j] - r.n[j] * k;
+        } else {
+            const float x0 = clamp01(dot3(r.e0[0], r.e0[1], r.e0[2], p0[0], p0[1], p0[2]) * r.r0);
+            const float x1 = clamp01(dot3(r.e1[0], r.e1[1], r.e1[2], p1[0], p1[1], p1[2]) * r.r1);
+            const float x2 = clamp01(dot3(r.e2[0], r.e2[1], r.e2[2], p2[0], p2[1], p2[2]) * r.r2);
+            const float E0 = edge_d2(r.e0, x0, p0[0], p0[1], p0[2]);
+            const float E1 = edge_d2(r.e1, x1, p1[0], p1[1], p1[2]);
+            const float E2 = edge_d2(r.e2, x2, p2[0], p2[1], p2[2]);
+            const bool first = E0 <= E1 && E0 <= E2, second = E1 <= E2;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float v = first ? r.a[j] : second ? r.b[j] : r.c[j];
+                const float e = first ? r.e0[j] : second ? r.e1[j] : r.e2[j];
+                const float x = first ? x0 : second ? x1 : x2;
+                h[j] = v + e * x;
+            }
+        }
+    }
+    dist[i] = finish(__uint_as_float(a.y), SIGNED ? a.z : 0u);
+    hit[i * 3 + 0] = h[0];
+    hit[i * 3 + 1] = h[1];
+    hit[i * 3 + 2] = h[2];
+    tidx[i] = (int32_t)a.x;
+}
+
 // chunks of one pass of `count` triangles for n points: as many as bring the grid to kMeshTargetBlocks workgroups when n is
 // small, one (no atomics beyond a pair per point and pass) once the point blocks alone reach that
-[[maybe_unused]] void mesh_chunks(int64_t n, int32_t count, int32_t &chunk_len, int32_t &chunks) {
+void mesh_chunks(int64_t n, int32_t count, int32_t &chunk_len, int32_t &chunks) {
     const int64_t bx = (n + kMeshPointsPerBlock - 1) / kMeshPointsPerBlock;
     int64_t want = (kMeshTargetBlocks + bx - 1) / bx;
     const int64_t most = (count + kMeshGranule - 1) / kMeshGranule;
@@ -362,6 +495,45 @@ hipError_t mesh_sdf_dispatch(int64_t n, int64_t t, const float *points, const fl
     }
     return hipSuccess;
 #endif
+}
+
+size_t mesh_closest_workspace(int64_t n, int64_t t) {
+    if (n <= 0) return 0;
+    const int64_t recs = t < kMeshPass ? t : kMeshPass;
+    return (size_t)recs * sizeof(TriRecord) + (size_t)n * sizeof(uint4);
+}
+
+hipError_t mesh_closest_dispatch(int64_t n, int64_t t, const float *points, const float *tris, bool is_signed, float *dist,
+                                 float *hit, int32_t *tidx, void *workspace, hipStream_t s) {
+    const dim3 block(kMeshBlock);
+    const dim3 per_point((uint32_t)((n + kMeshBlock - 1) / kMeshBlock));
+    const int64_t recs = t < kMeshPass ? t : kMeshPass;
+    TriRecord *rec = static_cast<TriRecord *>(workspace);
+    uint4 *acc = reinterpret_cast<uint4 *>(static_cast<char *>(workspace) + (size_t)recs * sizeof(TriRecord));
+    const uint32_t bx = (uint32_t)((n + kMeshPointsPerBlock - 1) / kMeshPointsPerBlock);
+    hipLaunchKernelGGL(mesh_closest_fill_kernel, per_point, block, 0, s, acc, n);
+    if (hipError_t e = hipGetLastError()) return e;
+    for (int64_t first = 0; first < t; first += kMeshPass) {
+        const int32_t count = (int32_t)(t - first < kMeshPass ? t - first : kMeshPass);
+        hipLaunchKernelGGL(mesh_sdf_prologue_kernel, dim3((uint32_t)((count + kMeshBlock - 1) / kMeshBlock)), block, 0, s,
+                           tris + (size_t)first * 9, rec, count);
+        if (hipError_t e = hipGetLastError()) return e;
+        int32_t chunk_len = 0, chunks = 0;
+        mesh_chunks(n, count, chunk_len, chunks);
+        const dim3 grid(bx, (uint32_t)chunks);
+        if (is_signed)
+            hipLaunchKernelGGL(mesh_closest_pair_kernel<true>, grid, block, 0, s, points, rec, count, chunk_len,
+                               (int32_t)first, acc, n);
+        else
+            hipLaunchKernelGGL(mesh_closest_pair_kernel<false>, grid, block, 0, s, points, rec, count, chunk_len,
+                               (int32_t)first, acc, n);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (is_signed)
+        hipLaunchKernelGGL(mesh_closest_finish_kernel<true>, per_point, block, 0, s, points, tris, acc, dist, hit, tidx, n);
+    else
+        hipLaunchKernelGGL(mesh_closest_finish_kernel<false>, per_point, block, 0, s, points, tris, acc, dist, hit, tidx, n);
+    return hipGetLastError();
 }
 
 }  // namespace shacira

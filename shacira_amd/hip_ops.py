@@ -963,3 +963,33 @@ def mesh_sdf(points, triangles):
         rc = L.shacira_mesh_sdf(N, T, _ptr(points), _ptr(triangles), _ptr(sdf), _ptr(ws), nbytes, _stream(points))
     _lib.check(rc, "mesh_sdf")
     return sdf
+
+
+def mesh_closest(points, triangles, signed=True):
+    """(dist [N] fp32, hit [N, 3] fp32, tidx [N] int32) of ``points`` [N, 3] against the triangles [T, 3, 3]: the distance to
+    the nearest non-degenerate triangle (negative inside when ``signed``: the bits of ``mesh_sdf``; otherwise its absolute
+    value, and no ray stabbing is executed), the closest point and the triangle it lies on (lowest index among equals, -1 and
+    ``hit = points`` when there is none). One pass over the N x T pairs (include/shacira_hip.h, shacira_mesh_closest)."""
+    _need_gpu(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"shacira_amd: points must be [N, 3], got {tuple(points.shape)}")
+    if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
+        raise RuntimeError(f"shacira_amd: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+    dev = points.device
+    points = points.detach().to(dtype=torch.float32).contiguous()
+    triangles = triangles.detach().to(device=dev, dtype=torch.float32).contiguous()
+    N, T = points.shape[0], triangles.shape[0]
+    dist = torch.empty((N,), dtype=torch.float32, device=dev)
+    hit = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    tidx = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N == 0:
+        return dist, hit, tidx
+    flags = _lib.MESH_CLOSEST_SIGNED if signed else 0
+    L = _lib.lib()
+    with _on_device(dev):
+        nbytes = int(L.shacira_mesh_closest_workspace_bytes(N, T, flags))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_mesh_closest(N, T, _ptr(points), _ptr(triangles), flags, _ptr(dist), _ptr(hit), _ptr(tidx), _ptr(ws),
+                                    nbytes, _stream(points))
+    _lib.check(rc, "mesh_closest")
+    return dist, hit, tidx

@@ -25,18 +25,16 @@ def _edge_d2(e, x, p):
     return (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]
 
 
-def mesh_sdf_torch(points: torch.Tensor, triangles: torch.Tensor):
-    """The contract of ``shacira_mesh_sdf`` in fp32 torch ops, every operator rounding once (no fused multiply-add), blocked
-    over the points: [N] fp32 on the device of ``points``. Bit-equal to the kernel for finite inputs."""
-    points = points.detach().to(torch.float32)
-    tri = triangles.detach().to(device=points.device, dtype=torch.float32)
+def _mesh_blocks(points, tri, signed=True, winner=False):
+    """The pair pass of the contract in fp32 torch ops, every operator rounding once (no fused multiply-add), blocked over
+    the points. Yields per block ``(start, stop, least, index, inside)``: the least d2 over the candidate triangles (+inf if
+    there are none), with ``winner`` the lowest index that attains it (-1 if none, int64), with ``signed`` the ray-stabbing
+    verdict (else None). ``points`` [N, 3] and ``tri`` [T, 3, 3] are fp32 on one device, N > 0 and T > 0."""
+    dev = points.device
     N, T = points.shape[0], tri.shape[0]
-    out = torch.full((N,), float("inf"), dtype=torch.float32, device=points.device)
-    if N == 0 or T == 0:
-        return out
-    one = torch.ones((), dtype=torch.float32, device=points.device)
-    zero = torch.zeros((), dtype=torch.float32, device=points.device)
-    inf = torch.full((), float("inf"), dtype=torch.float32, device=points.device)
+    one = torch.ones((), dtype=torch.float32, device=dev)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    inf = torch.full((), float("inf"), dtype=torch.float32, device=dev)
     # per triangle, [1, T]
     a, b, c = ([tri[None, :, v, k] for k in range(3)] for v in range(3))
     e0 = [b[k] - a[k] for k in range(3)]
@@ -49,12 +47,13 @@ def mesh_sdf_torch(points: torch.Tensor, triangles: torch.Tensor):
     valid = (n[0] != 0) | (n[1] != 0) | (n[2] != 0)
     g = [-e2[k] for k in range(3)]
     per_dir = []
-    for d in _DIRECTIONS:
-        dv = [torch.full((), x, dtype=torch.float32, device=points.device) for x in d]
+    for d in _DIRECTIONS if signed else ():
+        dv = [torch.full((), x, dtype=torch.float32, device=dev) for x in d]
         w = _cross(dv, g)
         det = _dot(e0, w)
         det64 = det.to(torch.float64)
         per_dir.append((dv, w, one / det, ~((det64 > -1e-8) & (det64 < 1e-8))))
+    order = torch.arange(T, device=dev)[None] if winner else None
     block = max(1, _BLOCK_PAIRS // T)
     for start in range(0, N, block):
         p = [points[start:start + block, k, None] for k in range(3)]          # [B, 1]
@@ -70,19 +69,43 @@ def mesh_sdf_torch(points: torch.Tensor, triangles: torch.Tensor):
         least = torch.where(valid, d2, inf)
         # fminf ignores NaN operands: replace them with +inf before the (NaN-propagating) reduction
         least = torch.where(torch.isnan(least), inf, least)
-        # sqrtf is correctly rounded; torch's vectorised host sqrt is not always. Through fp64 it is: the root of an fp32 value
-        # is at least 2^-50 (relative) away from an fp32 rounding boundary, further than the fp64 root's own error
-        dist = least.amin(dim=1).double().sqrt().float()
-        q = _cross(p0, e0)
-        tau = _dot(g, q)
-        inside = torch.ones(dist.shape, dtype=torch.bool, device=points.device)
-        for dv, w, inv, live in per_dir:
-            u = _dot(p0, w) * inv
-            v = _dot(dv, q) * inv
-            t = tau * inv
-            hit = live & ~((u < 0) | (u > 1)) & ~((v < 0) | (u + v > 1))
-            inside &= (hit & (t >= 0)).any(dim=1) & (hit & ~(t >= 0)).any(dim=1)
-        out[start:start + block] = torch.where(inside, -dist, dist)
+        best = least.amin(dim=1)
+        index = None
+        if winner:   # "replace iff d2 < best" from +inf over ascending indices: the first index of the minimum, none at +inf
+            index = torch.where((least == best[:, None]) & (least < inf), order, T).amin(dim=1)
+            index = torch.where(index == T, -1, index)
+        inside = None
+        if signed:
+            q = _cross(p0, e0)
+            tau = _dot(g, q)
+            inside = torch.ones(best.shape, dtype=torch.bool, device=dev)
+            for dv, w, inv, live in per_dir:
+                u = _dot(p0, w) * inv
+                v = _dot(dv, q) * inv
+                t = tau * inv
+                hit = live & ~((u < 0) | (u > 1)) & ~((v < 0) | (u + v > 1))
+                inside &= (hit & (t >= 0)).any(dim=1) & (hit & ~(t >= 0)).any(dim=1)
+        yield start, start + block, best, index, inside
+
+
+def _root(d2):
+    """sqrtf is correctly rounded; torch's vectorised host sqrt is not always. Through fp64 it is: the root of an fp32 value
+    is at least 2^-50 (relative) away from an fp32 rounding boundary, further than the fp64 root's own error."""
+    return d2.double().sqrt().float()
+
+
+def mesh_sdf_torch(points: torch.Tensor, triangles: torch.Tensor):
+    """The contract of ``shacira_mesh_sdf`` in fp32 torch ops, every operator rounding once (no fused multiply-add), blocked
+    over the points: [N] fp32 on the device of ``points``. Bit-equal to the kernel for finite inputs."""
+    points = points.detach().to(torch.float32)
+    tri = triangles.detach().to(device=points.device, dtype=torch.float32)
+    N, T = points.shape[0], tri.shape[0]
+    out = torch.full((N,), float("inf"), dtype=torch.float32, device=points.device)
+    if N == 0 or T == 0:
+        return out
+    for start, stop, least, _, inside in _mesh_blocks(points, tri):
+        dist = _root(least)
+        out[start:stop] = torch.where(inside, -dist, dist)
     return out
 
 
