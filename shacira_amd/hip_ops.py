@@ -940,10 +940,9 @@ def octree_backward(coords, levels, feature_dim, grad_output, multiscale_sum, fe
 
 
 # ---- mesh to signed distance (include/shacira_hip.h, shacira_mesh_sdf) -------------------------------------------------------
-def mesh_sdf(points, triangles):
-    """Signed distance [N] fp32 of ``points`` [N, 3] to the triangles [T, 3, 3] (the vertices a, b, c of each: ``V[F]``),
-    negative inside by 13-direction ray stabbing: the reference's ``_C.external.mesh_to_sdf_cuda``. Operands that are not
-    contiguous fp32 are copied; ``triangles`` is moved to the device of ``points``. T == 0 gives +inf."""
+def _mesh_operands(points, triangles):
+    """The checked operands of the two mesh calls as contiguous fp32 on the device of ``points``: (points, triangles, N, T,
+    device)."""
     _need_gpu(points)
     if points.dim() != 2 or points.shape[1] != 3:
         raise RuntimeError(f"shacira_amd: points must be [N, 3], got {tuple(points.shape)}")
@@ -953,6 +952,14 @@ def mesh_sdf(points, triangles):
     points = points.detach().to(dtype=torch.float32).contiguous()
     triangles = triangles.detach().to(device=dev, dtype=torch.float32).contiguous()
     N, T = points.shape[0], triangles.shape[0]
+    return points, triangles, N, T, dev
+
+
+def mesh_sdf(points, triangles):
+    """Signed distance [N] fp32 of ``points`` [N, 3] to the triangles [T, 3, 3] (the vertices a, b, c of each: ``V[F]``),
+    negative inside by 13-direction ray stabbing: the reference's ``_C.external.mesh_to_sdf_cuda``. Operands that are not
+    contiguous fp32 are copied; ``triangles`` is moved to the device of ``points``. T == 0 gives +inf."""
+    points, triangles, N, T, dev = _mesh_operands(points, triangles)
     sdf = torch.empty((N,), dtype=torch.float32, device=dev)
     if N == 0:
         return sdf
@@ -970,15 +977,7 @@ def mesh_closest(points, triangles, signed=True):
     the nearest non-degenerate triangle (negative inside when ``signed``: the bits of ``mesh_sdf``; otherwise its absolute
     value, and no ray stabbing is executed), the closest point and the triangle it lies on (lowest index among equals, -1 and
     ``hit = points`` when there is none). One pass over the N x T pairs (include/shacira_hip.h, shacira_mesh_closest)."""
-    _need_gpu(points)
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise RuntimeError(f"shacira_amd: points must be [N, 3], got {tuple(points.shape)}")
-    if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
-        raise RuntimeError(f"shacira_amd: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
-    dev = points.device
-    points = points.detach().to(dtype=torch.float32).contiguous()
-    triangles = triangles.detach().to(device=dev, dtype=torch.float32).contiguous()
-    N, T = points.shape[0], triangles.shape[0]
+    points, triangles, N, T, dev = _mesh_operands(points, triangles)
     dist = torch.empty((N,), dtype=torch.float32, device=dev)
     hit = torch.empty((N, 3), dtype=torch.float32, device=dev)
     tidx = torch.empty((N,), dtype=torch.int32, device=dev)

@@ -1,5 +1,6 @@
 """Helper, not a test: a numpy restatement of the mesh-to-SDF contract (include/shacira_hip.h, shacira_mesh_sdf) in
-np.float32, one rounding per operator, vectorised over (points, triangles) in blocks; and the meshes the tests use."""
+np.float32, one rounding per operator, vectorised over (points, triangles) in blocks; and the meshes, the point batch and the
+bit view that the mesh tests share."""
 import numpy as np
 
 F32 = np.float32
@@ -141,3 +142,31 @@ def box_sdf(points, half=0.5):
     """Exact signed distance to the cube [-half, half]^3 in fp64."""
     q = np.abs(np.asarray(points, dtype=np.float64)) - half
     return np.linalg.norm(np.maximum(q, 0.0), axis=1) + np.minimum(q.max(axis=1), 0.0)
+
+
+# ---- what the mesh tests share ----------------------------------------------------------------------------------------------
+SIZES = (1, 63, 64, 65, 4099)
+_POINTS = np.random.default_rng(21).uniform(-1, 1, (SIZES[-1], 3)).astype(F32)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=F32).view(np.uint32)
+
+
+def _triangles(name):
+    if name == "one":
+        return np.asarray([[[-0.4, -0.3, 0.1], [0.5, -0.2, -0.1], [0.1, 0.6, 0.2]]], dtype=F32)
+    if name == "cube":
+        V, F = cube(0.5)
+        return V[F]
+    if name == "cube x6":
+        V, F = cube(0.5)
+        return np.tile(V[F], (6, 1, 1))
+    if name == "soup":
+        return soup(37, seed=3)
+    level, radius = {"ico2": (2, 0.7), "ico4": (4, 0.7), "ico5+1": (5, 0.7)}[name]
+    V, F = icosphere(level, radius)
+    tri = V[F]
+    if name == "ico5+1":      # one more (degenerate: a point) than a multiple of the chunk granule, across two passes
+        tri = np.concatenate([tri, np.full((1, 3, 3), 0.25, dtype=F32)])
+    return tri

@@ -14,10 +14,10 @@ import torch
 
 import mesh_closest_ref as cref
 import mesh_sdf_ref as ref
+from mesh_sdf_ref import SIZES, _POINTS, _bits, _triangles
 
 pytestmark = pytest.mark.gpu
 EPS = float(np.finfo(np.float32).eps)
-SIZES = (1, 63, 64, 65, 4099)
 SIGNED = (True, False)
 
 
@@ -29,30 +29,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def _triangles(name):
-    if name == "one":
-        return np.asarray([[[-0.4, -0.3, 0.1], [0.5, -0.2, -0.1], [0.1, 0.6, 0.2]]], dtype=np.float32)
-    if name == "cube":
-        V, F = ref.cube(0.5)
-        return V[F]
-    if name == "cube x6":
-        V, F = ref.cube(0.5)
-        return np.tile(V[F], (6, 1, 1))
-    if name == "soup":
-        return ref.soup(37, seed=3)
-    level, radius = {"ico2": (2, 0.7), "ico4": (4, 0.7), "ico5+1": (5, 0.7)}[name]
-    V, F = ref.icosphere(level, radius)
-    tri = V[F]
-    if name == "ico5+1":      # one more (degenerate: a point) than a multiple of the chunk granule, across two passes
-        tri = np.concatenate([tri, np.full((1, 3, 3), 0.25, dtype=np.float32)])
-    return tri
-
-
-_POINTS = np.random.default_rng(21).uniform(-1, 1, (SIZES[-1], 3)).astype(np.float32)
 _CASES = {}
 
 

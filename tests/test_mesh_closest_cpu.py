@@ -22,30 +22,11 @@ import torch
 import mesh_closest_ref as cref
 import mesh_sdf_ref as ref
 from conftest import ROOT
+from mesh_sdf_ref import _POINTS as POINTS, _bits, _triangles
 from shacira_amd import _lib
 from shacira_amd.wisp.ops import mesh as mesh_ops
 
 EPS = float(np.finfo(np.float32).eps)
-POINTS = np.random.default_rng(21).uniform(-1, 1, (4099, 3)).astype(np.float32)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def _triangles(name):
-    if name == "one":
-        return np.asarray([[[-0.4, -0.3, 0.1], [0.5, -0.2, -0.1], [0.1, 0.6, 0.2]]], dtype=np.float32)
-    if name in ("cube", "lattice"):
-        V, F = ref.cube(0.5)
-        return V[F]
-    if name == "cube x6":
-        V, F = ref.cube(0.5)
-        return np.tile(V[F], (6, 1, 1))
-    if name == "soup":
-        return ref.soup(37, seed=3)
-    V, F = ref.icosphere(2, 0.7)
-    return V[F]
 
 
 _CASES = {}
@@ -55,7 +36,7 @@ def _case(name):
     """(points, triangles, {signed: restatement}), computed once."""
     if name not in _CASES:
         points = ref.lattice(9) if name == "lattice" else POINTS
-        tri = _triangles(name)
+        tri = _triangles("cube" if name == "lattice" else name)
         _CASES[name] = (points, tri, {s: cref.mesh_closest_ref(points, tri, signed=s) for s in (True, False)})
     return _CASES[name]
 

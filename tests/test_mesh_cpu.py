@@ -20,14 +20,11 @@ import torch
 
 import mesh_sdf_ref as ref
 from conftest import ROOT
+from mesh_sdf_ref import _bits
 from shacira_amd import _lib
 from shacira_amd.wisp.ops import mesh as mesh_ops
 
 EPS = float(np.finfo(np.float32).eps)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
 
 
 def _sdf(V, F, points, **kw):
