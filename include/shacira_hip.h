@@ -502,6 +502,67 @@ SHACIRA_API int shacira_mesh_closest(int64_t num_points, int64_t num_triangles, 
                                      size_t workspace_bytes, void *stream);
 
 /*
+ * Mesh to occupancy (ABI 11, additive): the triangles rasterised into the dense occupancy of one octree level. The reference
+ * gets there by sampling (wisp/ops/spc/conversions.py mesh_to_octree: surface samples plus a copy jittered by
+ * +-1 / 2^(level + 1) in cube coordinates, a quarter of a cell, both quantised); this call computes such a set exactly and
+ * deterministically. The limit of the reference's sampling is the set of margin 0.25 (a jittered sample lies within 0.75 cell,
+ * per axis, of the centre of its cell); a larger margin gives a superset of it.
+ *
+ *   triangles        [T, 3, 3] fp32, the layout of shacira_mesh_sdf, in the cube's coordinates [-1, 1]^3
+ *   level            0 <= level <= SHACIRA_OCTREE_MAX_LEVEL (the bound of the dense grids of the ray kernels, too); G = 2^level
+ *   margin           fp32, finite, >= 0, in cells
+ *   occupancy_words  out, uint32 [ceil(G^3 / 32)]: bit (key & 31) of word (key >> 5), key = (x * G + y) * G + z -- the
+ *                    occupancy_host layout of shacira_octree_forward
+ *   occupancy_grid   out, may be NULL: uint8 [G][G][G] indexed [x][y][z], 1 where the bit is set, 0 elsewhere (what the ray
+ *                    kernels and OctreeAS.occupancy_grid hold); expanded from the words by a finishing kernel; 16-byte aligned
+ * Both outputs are overwritten (zeroed by the call).
+ *
+ * The set: cell (i, j, k) is set iff some valid triangle overlaps the CLOSED cube with centre (i + .5, j + .5, k + .5) and
+ * half-extent H = 0.5 + margin, both in grid units g = (v + 1) * (G / 2): the 13-axis separating-axis test (three cube axes,
+ * the triangle normal, nine edge x axis cross products) in its projected form -- an integer bounding box, the plane slab and
+ * three 2-D edge-function triples -- with closed comparisons throughout: touching counts. All arithmetic is fp32 without
+ * contraction, one rounding per operator, cross(x, y) as in the shacira_mesh_sdf contract, in these fixed shapes:
+ * Per triangle (a, b, c as given):
+ *   valid  iff  cross(b - a, a - c) has a non-zero component (the record flag of shacira_mesh_sdf, on the vertices as given)
+ *          and all nine grid-unit coordinates are finite. An invalid triangle marks nothing.
+ *   A = (a + 1) * (G / 2), B, C alike (component-wise; G / 2 is exact, 0.5 at level 0);  H = 0.5f + margin
+ *   E0 = B - A, E1 = C - B, E2 = A - C;  N = cross(E0, E1);  rN = H * ((|Nx| + |Ny|) + |Nz|)
+ *   cube axes, per axis c:  lo_c = fmaxf(ceilf((fminf(fminf(A_c, B_c), C_c) - H) - 0.5f), 0)
+ *                           hi_c = fminf(floorf((fmaxf(fmaxf(A_c, B_c), C_c) + H) - 0.5f), G - 1)
+ *          cell index i passes iff lo_c <= i <= hi_c: the integers with i + 0.5 in [min - H, max + H], CLIPPED to the grid.
+ *          Geometry outside the cube therefore marks nothing (a stated deviation: the reference clamps outside samples into
+ *          the border cells).
+ *   projection k = 0, 1, 2 drops axis k: (u, v) = (y, z), (z, x), (x, y);  sigma_k = N_k >= 0 ? +1 : -1;
+ *          edge i = 0, 1, 2 starts at P_i = A, B, C:  mu = -sigma_k * E_i[v],  mv = sigma_k * E_i[u]  (exact),
+ *          r = H * (|mu| + |mv|)
+ * Per (cell, triangle) pair, centre p = (i + .5, j + .5, k + .5) (exact):
+ *   plane     s = (Nx * (px - Ax) + Ny * (py - Ay)) + Nz * (pz - Az);   passes iff  -rN <= s  and  s <= rN
+ *   edges     f = (mu * (p_u - P_i[u]) + mv * (p_v - P_i[v])) + r;      passes iff  f >= 0      (all nine)
+ * A NaN in any of these (overflowing products of far-away vertices) fails its comparison and the pair marks nothing.
+ * With sigma from the sign of N_k, a projection that degenerates to a segment (N_k == 0) still gives the slab around that
+ * segment, which is what the three edge x axis products of that projection test.
+ *
+ * The predicate belongs to one (cell, triangle) pair and the combine is an OR: any split of the work over passes, workgroups
+ * and lanes gives the same bits, and two calls give identical outputs. The call splits it into COLUMN WORDS -- one (x, y)
+ * column of a triangle's bounding box crossed with one 32-bit word of its z range -- one lane and at most one atomicOr each,
+ * lanes found by binary search in the exclusive scan of the per-triangle unit counts. tests/mesh_voxelize_ref.py restates
+ * the formulas in numpy and reproduces the cell set exactly.
+ *
+ *   workspace  shacira_mesh_voxelize_workspace_bytes(T, level) bytes, 16-byte aligned: the 192-byte records and the 64-bit
+ *              unit offsets of ONE pass of at most SHACIRA_MESH_VOXELIZE_PASS_TRIANGLES triangles (6.25 MiB whatever T).
+ *              0 when T == 0 (workspace may then be NULL) or the arguments are invalid. The call initialises what it reads.
+ * Bounds: 0 <= T < 2^31. Validation happens before any HIP call: a bad count, level or margin (negative, NaN, infinite) and
+ * NULL or misaligned operands return SHACIRA_EINVAL, a workspace below the query SHACIRA_EWORKSPACE. T == 0 zeroes the outputs.
+ * Everything runs on `stream`, which the call SYNCHRONISES once per pass (the host reads the pass's unit count to size the
+ * launch): not capturable into a graph, unlike shacira_mesh_sdf. No allocation.
+ */
+#define SHACIRA_MESH_VOXELIZE_PASS_TRIANGLES 32768
+SHACIRA_API size_t shacira_mesh_voxelize_workspace_bytes(int64_t num_triangles, int level);
+SHACIRA_API int shacira_mesh_voxelize(int64_t num_triangles, const float *triangles, int level, float margin,
+                                      uint32_t *occupancy_words, uint8_t *occupancy_grid, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

@@ -19,6 +19,8 @@ TRIPLANE_GRAD_PLANES, TRIPLANE_GRAD_COORDS = 1, 2
 OCTREE_GRAD_FEATURES, OCTREE_GRAD_COORDS = 1, 2
 MESH_SDF_PASS_TRIANGLES, MESH_SDF_CHUNK_GRANULE = 16384, 32   # SHACIRA_MESH_SDF_* of the header
 MESH_CLOSEST_SIGNED = 1
+MESH_VOXELIZE_PASS_TRIANGLES = 32768                          # SHACIRA_MESH_VOXELIZE_PASS_TRIANGLES
+OCTREE_MAX_LEVEL = 10                                         # SHACIRA_OCTREE_MAX_LEVEL
 
 _lock = threading.Lock()
 _lib = None
@@ -61,6 +63,8 @@ SIGNATURES = {
     "shacira_mesh_sdf": (_i, [_i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "shacira_mesh_closest_workspace_bytes": (_sz, [_i64, _i64, ctypes.c_int32]),
     "shacira_mesh_closest": (_i, [_i64, _i64, _p, _p, ctypes.c_int32, _p, _p, _p, _p, _sz, _p]),
+    "shacira_mesh_voxelize_workspace_bytes": (_sz, [_i64, _i]),
+    "shacira_mesh_voxelize": (_i, [_i64, _p, _i, _f, _p, _p, _p, _sz, _p]),
     "shacira_find_depth_bound": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),

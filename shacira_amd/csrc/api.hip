@@ -542,6 +542,28 @@ int shacira_mesh_closest(int64_t num_points, int64_t num_triangles, const float 
                                       dist, hit, tidx, workspace, (hipStream_t)stream);
 }
 
+// ---- mesh to occupancy ---------------------------------------------------------------------------------------------------
+static bool voxelize_args_ok(int64_t num_triangles, int level) {
+    return num_triangles >= 0 && num_triangles <= INT32_MAX && level >= 0 && level <= SHACIRA_OCTREE_MAX_LEVEL;
+}
+
+size_t shacira_mesh_voxelize_workspace_bytes(int64_t num_triangles, int level) {
+    if (!voxelize_args_ok(num_triangles, level)) return 0;
+    return mesh_voxelize_workspace(num_triangles);
+}
+
+int shacira_mesh_voxelize(int64_t num_triangles, const float *triangles, int level, float margin,
+                          uint32_t *occupancy_words, uint8_t *occupancy_grid, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    if (!voxelize_args_ok(num_triangles, level) || !(margin >= 0.f) || std::isinf(margin)) return SHACIRA_EINVAL;
+    if (!occupancy_words || (num_triangles > 0 && !triangles)) return SHACIRA_EINVAL;
+    if (level >= 2 && ((uintptr_t)occupancy_grid & 15u)) return SHACIRA_EINVAL;     // written 16 bytes at a time
+    const size_t need = mesh_voxelize_workspace(num_triangles);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
+    return (int)mesh_voxelize_dispatch(num_triangles, triangles, level, margin, occupancy_words, occupancy_grid, workspace,
+                                       (hipStream_t)stream);
+}
+
 // ---- sphere tracing over ray packs ---------------------------------------------------------------------------------------
 static bool trace_counts_ok(int64_t num_packs, int64_t num_nugs) {
     return num_packs >= 0 && num_nugs >= 0 && num_packs <= INT32_MAX && num_nugs <= INT32_MAX && num_packs <= num_nugs;

@@ -146,6 +146,12 @@ size_t mesh_closest_workspace(int64_t n, int64_t t);
 hipError_t mesh_closest_dispatch(int64_t n, int64_t t, const float *points, const float *tris, bool is_signed, float *dist,
                                  float *hit, int32_t *tidx, void *workspace, hipStream_t s);
 
+// mesh_voxelize.hip: t triangles into the occupancy words of `level` (and the byte grid when grid != NULL); arguments checked by
+// the entry point. Synchronises the stream once per pass of triangles (the host reads the pass's unit count)
+size_t mesh_voxelize_workspace(int64_t t);
+hipError_t mesh_voxelize_dispatch(int64_t t, const float *tris, int level, float margin, uint32_t *words, uint8_t *grid,
+                                  void *workspace, hipStream_t s);
+
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
                                    const float *depth, int32_t *out, hipStream_t s);

@@ -992,3 +992,35 @@ def mesh_closest(points, triangles, signed=True):
                                     nbytes, _stream(points))
     _lib.check(rc, "mesh_closest")
     return dist, hit, tidx
+
+
+# ---- mesh to occupancy (include/shacira_hip.h, shacira_mesh_voxelize) ---------------------------------------------------------
+def mesh_voxelize(triangles, level, margin=0.5, with_grid=True):
+    """The triangles [T, 3, 3] (in [-1, 1]^3) rasterised into the occupancy of octree level ``level``: (words int32
+    [ceil(G^3 / 32)], grid bool [G, G, G] or None). A cell is set iff a non-degenerate triangle overlaps the closed cube of
+    half-extent ``0.5 + margin`` cells around its centre; geometry outside the cube marks nothing. ``words`` has the bit layout
+    of ``wisp.ops.octree``'s ``occupancy``, ``grid`` that of ``OctreeAS.occupancy_grid``. Deterministic."""
+    _need_gpu(triangles)
+    if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
+        raise RuntimeError(f"shacira_amd: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+    level, margin = int(level), float(margin)
+    if not 0 <= level <= _lib.OCTREE_MAX_LEVEL:
+        raise RuntimeError(f"shacira_amd: level must be in 0..{_lib.OCTREE_MAX_LEVEL}, got {level}")
+    if not 0.0 <= margin < float("inf"):
+        raise RuntimeError(f"shacira_amd: margin must be finite and >= 0, got {margin}")
+    dev = triangles.device
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("shacira_amd: mesh_voxelize synchronises its stream (the host reads a unit count per pass of "
+                           "triangles) and cannot be captured into a graph")
+    triangles = triangles.detach().to(dtype=torch.float32).contiguous()
+    T, G = triangles.shape[0], 1 << level
+    words = torch.empty(((G ** 3 + 31) // 32,), dtype=torch.int32, device=dev)
+    grid = torch.empty((G, G, G), dtype=torch.uint8, device=dev) if with_grid else None
+    L = _lib.lib()
+    with _on_device(dev):
+        nbytes = int(L.shacira_mesh_voxelize_workspace_bytes(T, level))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_mesh_voxelize(T, _ptr(triangles), level, margin, _ptr(words), _ptr(grid), _ptr(ws), nbytes,
+                                     _stream(triangles))
+    _lib.check(rc, "mesh_voxelize")
+    return words, (grid.view(torch.bool) if with_grid else None)

@@ -9,7 +9,7 @@ import importlib
 import sys
 
 _ALIASES = [
-    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.geometric", "ops.differential", "ops.image", "ops.image.metrics", "core", "accelstructs", "accelstructs.aabb_as",
+    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.spc", "ops.geometric", "ops.differential", "ops.image", "ops.image.metrics", "core", "accelstructs", "accelstructs.aabb_as",
     "models", "models.grids", "models.grids.blas_grid", "models.grids.hash_grid", "models.grids.latent_grid",
     "models.grids.triplanar_grid", "models.grids.octree_grid",
     "models.grids.codebook_grid", "models.latent_decoders",

@@ -4,7 +4,7 @@ used by hash_grid.py:60-66 / latent_grid.py:70-76 through ``OctreeAS.make_dense`
 One dense occupancy level with Morton-ordered cell coordinates (``points``) so that ``dense_points`` / ``num_cells``
 / ``occupancy`` have the reference's shapes, plus -- SURVEY.md section 8 "next" row f2 -- the queries the NeRF pipeline
 makes of it: ``query``, ``raytrace``, ``raymarch`` ('ray' and 'voxel', octree_as.py:129-307) and
-``from_quantized_points`` (pruning, nerf.py:150-185). The reference answers them with kaolin's sparse-octree CUDA
+``from_quantized_points`` (pruning, nerf.py:150-185), and ``from_triangles``, the mesh rasterised by mesh_voxelize.hip. The reference answers them with kaolin's sparse-octree CUDA
 (un-vendored); here the occupied set is a dense [G, G, G] bit grid walked by the HIP kernels of render.hip.
 ``pidx`` values are Morton indices of the level's cells (the reference's index into its SPC point hierarchy).
 
@@ -90,20 +90,46 @@ class OctreeAS(BaseAS):
         grid[q[:, 0], q[:, 1], q[:, 2]] = True
         return cls(level, grid)
 
-    @classmethod
-    def from_pointcloud(cls, pointcloud: torch.Tensor, level: int):
-        """Occupied set = the cells of ``level`` holding a point of ``pointcloud`` [N, 3] in [-1, 1]^3, quantised with
-        ``query``'s floor(G * (x + 1) / 2) and clamped into the grid as kaolin's ``quantize_points`` does (a point on a far
-        face, x = 1, falls into the last cell). Points that are not finite are dropped."""
+    @staticmethod
+    def quantize_pointcloud(pointcloud: torch.Tensor, level: int):
+        """(cells int64 [M, 3], keep bool [N]): the cell of ``level`` of every finite point of ``pointcloud`` [N, 3] in
+        [-1, 1]^3, ``query``'s floor(G * (x + 1) / 2) clamped into the grid as kaolin's ``quantize_points`` does (a point on a
+        far face, x = 1, falls into the last cell); ``keep`` marks the points that are finite, the rows of ``cells``."""
         G = 1 << level
         cell = torch.floor(G * (pointcloud.float() + 1.0) / 2.0)
         keep = torch.isfinite(cell).all(dim=-1)
-        return cls.from_quantized_points(cell[keep].clamp(0, G - 1).long(), level)
+        return cell[keep].clamp(0, G - 1).long(), keep
+
+    @classmethod
+    def from_pointcloud(cls, pointcloud: torch.Tensor, level: int):
+        """Occupied set = the cells of ``level`` holding a point of ``pointcloud`` [N, 3] in [-1, 1]^3
+        (``quantize_pointcloud``). Points that are not finite are dropped."""
+        return cls.from_quantized_points(cls.quantize_pointcloud(pointcloud, level)[0], level)
+
+    @classmethod
+    def from_triangles(cls, vertices: torch.Tensor, faces: torch.Tensor, level: int, margin: float = 0.5):
+        """Occupied set = the cells of ``level`` that the mesh (``vertices`` [V, 3] in [-1, 1]^3, ``faces`` [F, 3]) touches:
+        a cell is set iff a non-degenerate triangle overlaps the closed cube of half-extent ``0.5 + margin`` cells around
+        its centre (the HIP rasteriser of mesh_voxelize.hip; contract: include/shacira_hip.h, shacira_mesh_voxelize).
+        Deterministic and free of holes. The reference's ``from_mesh`` samples instead: surface samples plus a copy jittered
+        by +-1 / 2^(level + 1) in cube coordinates, a QUARTER of a cell, whose limit is the set of ``margin = 0.25``; the
+        default ``margin = 0.5`` is a superset of it, about a third larger. Geometry outside the cube marks nothing where
+        the reference clamps it into the border cells. ``vertices`` and ``faces`` are kept in ``extent``, as the reference's
+        ``from_mesh`` keeps them; the tensors must be on the GPU."""
+        from ... import hip_ops
+        hip_ops._need_gpu(vertices, faces)
+        words, grid = hip_ops.mesh_voxelize(vertices[faces.long()], level, margin)
+        blas = cls(level, grid)
+        blas._packed = (blas.occupancy_grid, words)
+        blas.extent["vertices"] = vertices
+        blas.extent["faces"] = faces
+        return blas
 
     @classmethod
     def from_mesh(cls, *args, **kwargs):
-        raise NotImplementedError("OctreeAS.from_mesh needs OBJ loading and surface sampling, which are not part of this "
-                                  "package: sample the surface elsewhere and use from_pointcloud")
+        raise NotImplementedError("OctreeAS.from_mesh(path) is not implemented: load the mesh with wisp.ops.mesh.load_obj, "
+                                  "normalize(vertices, faces, 'sphere') it, move it to the GPU and call "
+                                  "OctreeAS.from_triangles(vertices, faces, level)")
 
     @classmethod
     def from_spc(cls, *args, **kwargs):
@@ -126,6 +152,16 @@ class OctreeAS(BaseAS):
     def occupancy_changed(self):
         """Drop the cached coarser levels: to be called after ``occupancy_grid`` was written in place."""
         self.__dict__.pop("_coarse", None)
+        self.__dict__.pop("_packed", None)
+
+    def packed_occupancy(self, level: int):
+        """The occupancy of ``level`` as packed int32 words (bit ``key & 31`` of word ``key >> 5``, key = (x * G + y) * G
+        + z) when the structure already holds them -- ``from_triangles`` keeps what the rasteriser wrote for ``max_level``
+        -- else None. Dropped with the grid they describe (a replaced or moved ``occupancy_grid``, ``occupancy_changed``)."""
+        packed = self.__dict__.get("_packed")
+        if packed is None or level != self.max_level or packed[0] is not self.occupancy_grid:
+            return None
+        return packed[1]
 
     def occupancy_at(self, level: int, device=None) -> torch.Tensor:
         """Dense bool [G, G, G] of ``level`` (G = 2^level) on ``device`` (default: where the grid lives)."""

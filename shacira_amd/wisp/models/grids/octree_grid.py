@@ -13,7 +13,9 @@ Differences, all stated:
     follow ``points_dual[l]``: ascending linear key (x * S + y) * S + z (``wisp.ops.octree``). That is not kaolin's order, so
     a reference checkpoint does not load;
   * the reference casts the table to fp16 for kaolin's kernel; the lookup here is fp32;
-  * ``interpolation_type='closest'``, ``from_mesh`` and ``from_spc`` raise ``NotImplementedError``;
+  * ``interpolation_type='closest'``, ``from_mesh`` and ``from_spc`` raise ``NotImplementedError``; a mesh comes in
+    through ``from_triangles`` (``load_obj`` -> ``normalize(..., 'sphere')`` -> ``from_triangles``), rasterised exactly
+    where the reference samples;
   * when ``self.blas`` is replaced (``OctreeAS.from_quantized_points`` on a new cell set), the next ``interpolate``
     rebuilds the index and carries every surviving corner's row over into new tables; corners that were not there before
     start at ``feature_bias``. The ``Parameter`` objects are replaced, so an optimizer has to be rebuilt after that (a
@@ -81,8 +83,15 @@ class OctreeGrid(BLASGrid):
         return cls(accelstruct=blas, feature_dim=feature_dim, base_lod=base_lod, num_lods=num_lods, **kwargs)
 
     @classmethod
+    def from_triangles(cls, vertices: torch.Tensor, faces: torch.Tensor, feature_dim: int, base_lod: int, num_lods: int = 1,
+                       margin: float = 0.5, **kwargs):
+        """Occupied cells = the cells of the finest level that the mesh touches (``OctreeAS.from_triangles``; GPU tensors)."""
+        blas = OctreeAS.from_triangles(vertices, faces, level=OctreeGrid.max_octree_lod(base_lod, num_lods), margin=margin)
+        return cls(accelstruct=blas, feature_dim=feature_dim, base_lod=base_lod, num_lods=num_lods, **kwargs)
+
+    @classmethod
     def from_mesh(cls, *args, **kwargs):
-        return OctreeAS.from_mesh(*args, **kwargs)     # raises, naming the reason
+        return OctreeAS.from_mesh(*args, **kwargs)     # raises, naming the way: load_obj, normalize, from_triangles
 
     @classmethod
     def from_spc(cls, *args, **kwargs):

@@ -133,7 +133,9 @@ def build_octree_level(blas, level) -> OctreeLevelIndex:
     bits, count = _pack_bits(flat)
     before = torch.cumsum(count, 0, dtype=torch.int64) - count
     corner_index = torch.stack([bits, before.to(torch.int32)], dim=-1).contiguous()
-    occupancy, _ = _pack_bits(occ.reshape(-1))
+    occupancy = blas.packed_occupancy(level)         # a rasterised mesh brings its words
+    if occupancy is None:
+        occupancy, _ = _pack_bits(occ.reshape(-1))
     return OctreeLevelIndex(level, blas.level_points(level).to(occ.device), points_dual, occupancy, corner_index)
 
 
