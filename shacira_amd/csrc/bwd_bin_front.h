@@ -80,8 +80,8 @@ __global__ __launch_bounds__(256) void transpose_grad_kernel(const T *__restrict
 // atomics; COUNT = true), parks the rows LEVEL-major in LDS and writes them out as 16-byte non-temporal vectors of
 // M = 16 / (4 F) consecutive samples of one level. The staging image gT is [L][NP][F] with the level pitch NP = N rounded
 // up to even, so that every vector is 16-byte aligned for any batch size. Bucket counts leave as ONE global atomic per
-// (workgroup, non-empty bucket) into totals[] -- the per-(tile, bucket) matrix and its scan are gone: the scatter pass
-// reserves its runs with returning atomics on per-bucket cursors instead.
+// (workgroup, non-empty bucket) into totals[]; the rows of cnt[counting tile][bucket] go to the bucket scan, which turns them
+// into the places of the scatter pass's runs (scan_run_offsets).
 constexpr int kFrontThreads = 512;
 // SORTED (round 6): the batch's plan is at hand -- `sorted4` = its 16-byte records {x, y, z, sample index} in block order. The
 // tile's samples are then records s0 .. s0 + TS: their gradient rows are GATHERED (row = the record's index; a row is whole
@@ -128,10 +128,10 @@ __global__ __launch_bounds__(kFrontThreads) void front16_kernel(LevelTable lt, B
     const int64_t tile0 = (int64_t)blockIdx.x * rounds;
     const int64_t tiles = (N + TS - 1) >> ts_log2;
     // the histogram is per ROUND: after each tile a thread moves its words (k = tid + j * 512 <-> (level k / 128, bucket
-    // k % 128)) to the tile's row of cnt[tile][bucket] -- what lets the scatter pass reserve its runs before it has ranked
-    // anything -- and keeps the workgroup's sums in registers for the totals
+    // k % 128)) to the tile's row of cnt[tile][bucket] -- what the bucket scan places the scatter pass's runs from -- and keeps
+    // the workgroup's sums in registers for the totals
     uint32_t hsum[HE];
-    uint32_t hacc[HE];   // items of the current SCATTER tile (cps counting tiles) so far: its runs are reserved in multiples of plan.pad
+    uint32_t hacc[HE];   // items of the current SCATTER tile (cps counting tiles) so far: its runs are multiples of plan.pad long
     // word k = tid + j * 512 <-> (level slot k / 128, bucket k % 128): the slot is uniform over a wave (128 = two waves), so
     // it is made a scalar and the two plan words come by scalar loads. (Round 4: with a lane-dependent index into the
     // by-value plan the compiler read the kernel arguments through VECTOR loads -- blevel[li] -> lv[..].nb -> bstart[li],
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(kFrontThreads) void front16_kernel(LevelTable lt, B
         if constexpr (COUNT) {
             // Counts leave as one row of cnt[counting tile][bucket] with the ACTUAL number of item units; the totals -- the bucket
             // bases -- take every (scatter tile, bucket) run rounded up to plan.pad units (line-aligned runs, plan.pad > 1: the
-            // scatter pass reserves its runs in such multiples; a workgroup's counting tiles are then whole scatter tiles, the
+            // bucket scan places the runs in such multiples; a workgroup's counting tiles are then whole scatter tiles, the
             // host makes `rounds` a multiple of cps)
             uint32_t *row = cnt + (size_t)(tile0 + r) * plan.total_buckets;
             const bool close = plan.pad > 1u && ((uint32_t)((tile0 + r + 1) % (int64_t)cps) == 0u || tile0 + r + 1 == tiles);
@@ -333,18 +333,100 @@ __global__ __launch_bounds__(kFrontThreads) void front16_kernel(LevelTable lt, B
 }
 
 // ------------------------------------------------------------------------------------------------- pass S
-// single block: bucket bases (exclusive scan of totals) and the consumer work list
+// Where every (scatter tile, bucket) run starts inside its bucket: the exclusive prefix, over the scatter tiles in front of it,
+// of the run lengths -- pad_round(sum of the tile's cps counting rows of cnt[counting tile][bucket]), what the counting pass
+// added to the bucket's total. Runs lie in a bucket in TILE order. (Before, a scatter workgroup drew the place of a run
+// from a cursor per bucket with one returning atomic: S1's planned call paid 720 K of them, 1 024 on every cursor word.)
+// A workgroup owns kScanCols consecutive buckets (lanes = consecutive columns of a row). Thread (chunk, column) walks
+// kScanRows consecutive counting rows of its column -- all loaded up front, from the chunk's last row once past the end --
+// and keeps the running offset in front of each row; wave w then scans column w's chunk sums across its 64 lanes.
+// The offset REPLACES the count in the first counting row of its scatter tile: a thread overwrites only words it has read
+// itself, and no other workgroup touches its columns. 32-bit: a bucket's units (the 64-bit part is the bucket's base).
+// Sized by measurement (profiles/scatter_prefix.md): a workgroup fetches one line per counting row whatever its width, so
+// narrower workgroups only multiply the line requests -- 8 columns x 16 rows per thread (88 workgroups on S1's 704 buckets)
+// took 11.7 us against 10.5 for 16 x 32 (44 workgroups), with workgroup 0 alone at 9.4.
+// Batches beyond kScanChunks * kScanRows counting rows (S1 at 2^20 samples: exactly that many) take several sweeps.
+constexpr int kScanThreads = 1024;
+constexpr int kScanCols = 16;                               // buckets per workgroup
+constexpr int kScanChunks = kScanThreads / kScanCols;       // chunks of rows per sweep
+constexpr int kScanRows = 32;                               // counting rows per thread and sweep (a multiple of cps)
+static_assert(kScanChunks == 64, "one wave scans one column's chunk sums");
+__device__ __forceinline__ void scan_run_offsets(uint32_t *__restrict__ cnt, uint32_t group, uint32_t nb, uint32_t pad,
+                                                 uint32_t cps, uint32_t cnt_rows) {
+    __shared__ uint32_t s_chunk[kScanCols][kScanChunks + 1];   // [column][chunk]: sums, then exclusive prefixes; [..][64]: the sweep's total
+    const uint32_t col = threadIdx.x % kScanCols, chunk = threadIdx.x / kScanCols;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t gb = group * kScanCols + col;
+    const bool live = gb < nb;
+    uint32_t *colp = cnt + (live ? gb : nb - 1u);
+    const uint32_t pm = pad - 1u;
+    uint32_t carry = 0;   // the column's run lengths of the sweeps before
+    for (uint32_t row0 = 0; row0 < cnt_rows; row0 += (uint32_t)(kScanChunks * kScanRows)) {
+        const uint32_t r0 = row0 + chunk * (uint32_t)kScanRows;
+        const uint32_t left = r0 < cnt_rows ? cnt_rows - r0 : 0u;
+        const uint32_t nvalid = left < (uint32_t)kScanRows ? left : (uint32_t)kScanRows;   // rows of this chunk inside the matrix
+        const uint32_t *p = colp + (size_t)(nvalid ? r0 : cnt_rows - 1u) * nb;
+        uint32_t v[kScanRows];
+#pragma unroll
+        for (int k = 0; k < kScanRows; ++k) {
+            v[k] = *p;
+            p += ((uint32_t)k + 1u < nvalid) ? nb : 0u;
+        }
+        uint32_t run = 0, acc = 0;
+#pragma unroll
+        for (int k = 0; k < kScanRows; ++k) {
+            const uint32_t h = ((uint32_t)k < nvalid) ? v[k] : 0u;
+            v[k] = run;          // (read below at the first row of a scatter tile only)
+            acc += h;
+            if ((((uint32_t)k + 1u) & (cps - 1u)) == 0u) {   // the scatter tile's last counting row (the batch's last tile may have fewer: zeros)
+                run += (acc + pm) & ~pm;
+                acc = 0;
+            }
+        }
+        s_chunk[col][chunk] = run;
+        __syncthreads();
+        {
+            const uint32_t t = s_chunk[wave][lane];
+            uint32_t incl = t;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t nbr = __shfl_up(incl, off, 64);
+                if (lane >= (uint32_t)off) incl += nbr;
+            }
+            s_chunk[wave][lane] = incl - t;
+            if (lane == 63) s_chunk[wave][kScanChunks] = incl;
+        }
+        __syncthreads();
+        const uint32_t off0 = carry + s_chunk[col][chunk];
+        carry += s_chunk[col][kScanChunks];
+        uint32_t *w = colp + (size_t)r0 * nb;   // (dereferenced inside the matrix only)
+#pragma unroll
+        for (int k = 0; k < kScanRows; ++k) {
+            if (((uint32_t)k & (cps - 1u)) == 0u && (uint32_t)k < nvalid && live) *w = off0 + v[k];
+            w += nb;
+        }
+        __syncthreads();   // s_chunk is refilled by the next sweep
+    }
+}
+
+// grid 1 + ceil(nb / kScanCols). Workgroups 1.. : the run offsets above. Workgroup 0: bucket bases (exclusive scan of totals)
+// and the consumer work list
 //   base[b]         first item of bucket b in the item array (base[nb] = total)
 //   unit_first[b]   first work unit of bucket b; unit_first[nb] = number of units
 //   unit_desc[u]    item range, bucket and level of work unit u
-__global__ __launch_bounds__(1024) void bin_scan_buckets_kernel(const uint32_t *__restrict__ totals,
-                                                                uint64_t *__restrict__ base,
-                                                                uint32_t *__restrict__ unit_first,
-                                                                UnitDesc *__restrict__ unit_desc, uint32_t nb,
-                                                                BinPlan plan,
-                                                                uint32_t *__restrict__ work_counter,
-                                                                unsigned long long *__restrict__ cursor,
-                                                                const uint32_t *__restrict__ gmax) {
+__global__ __launch_bounds__(kScanThreads) void bin_scan_buckets_kernel(const uint32_t *__restrict__ totals,
+                                                                        uint64_t *__restrict__ base,
+                                                                        uint32_t *__restrict__ unit_first,
+                                                                        UnitDesc *__restrict__ unit_desc, uint32_t nb,
+                                                                        BinPlan plan,
+                                                                        uint32_t *__restrict__ work_counter,
+                                                                        const uint32_t *__restrict__ gmax,
+                                                                        uint32_t *__restrict__ cnt, uint32_t cps,
+                                                                        uint32_t cnt_rows) {
+    if (blockIdx.x != 0) {
+        scan_run_offsets(cnt, blockIdx.x - 1u, nb, plan.pad, cps, cnt_rows);
+        return;
+    }
     __shared__ uint64_t s_items[kMaxBuckets + 2];
     __shared__ uint32_t s_units[kMaxBuckets + 2];
     __shared__ uint64_t s_wave_items[16];
@@ -353,7 +435,7 @@ __global__ __launch_bounds__(1024) void bin_scan_buckets_kernel(const uint32_t *
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) work_counter[0] = 0;   // the persistent consume pass fetches its units from here
     uint64_t c[2];
-    uint32_t u[2], lv_of[2], ck[2];
+    uint32_t u[2], lv_of[2], ck[2], gm_of[2];   // gm_of: the level's max |grad| bits, loaded with the totals (not behind the scan)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const uint32_t b = 2 * t + k;
@@ -368,6 +450,7 @@ __global__ __launch_bounds__(1024) void bin_scan_buckets_kernel(const uint32_t *
         for (uint32_t q = 1; q < SHACIRA_MAX_LODS; ++q)
             if (q < plan.nbl && plan.bstart[q] <= b) lvl = plan.blevel[q];
         lv_of[k] = lvl;
+        gm_of[k] = gmax != nullptr ? gmax[lvl] : 0u;
         ck[k] = plan.chunk;   // (one unit size for every level of a plan)
         u[k] = (c[k] >> 32) ? (uint32_t)((c[k] + ck[k] - 1) / ck[k]) : (c[k] ? ((uint32_t)c[k] - 1u) / ck[k] + 1u : 0u);
     }
@@ -397,7 +480,6 @@ __global__ __launch_bounds__(1024) void bin_scan_buckets_kernel(const uint32_t *
     __syncthreads();
     for (uint32_t b = t; b <= nb; b += 1024) {
         base[b] = s_items[b];          // entries >= nb hold the grand totals (zero counts beyond nb)
-        cursor[b] = s_items[b];        // the scatter pass reserves its runs from here (returning atomics)
         unit_first[b] = s_units[b];
     }
 #pragma unroll
@@ -405,7 +487,7 @@ __global__ __launch_bounds__(1024) void bin_scan_buckets_kernel(const uint32_t *
         const uint32_t b = 2 * t + k;
         if (b < nb) {
             const uint32_t lvl = lv_of[k];
-            const uint32_t gm = (gmax != nullptr && u[k] > 0) ? gmax[lvl] : 0u;
+            const uint32_t gm = gm_of[k];
             for (uint32_t q = 0; q < u[k]; ++q) {
                 UnitDesc d;
                 d.begin = s_items[b] + (uint64_t)q * ck[k];

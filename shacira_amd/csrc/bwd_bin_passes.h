@@ -8,9 +8,9 @@
 namespace shacira {
 
 // ------------------------------------------------------------------------------------------------- pass B
-// Gradients from the transposed image gT [L][NP][F], grid (tiles, binned levels). A (tile, bucket) run is reserved with one
-// returning atomic on the bucket's cursor (set to the bucket's base by the bucket scan): runs of different tiles land in
-// the bucket in arrival order -- the consumer's fixed-point sums do not depend on it.
+// Gradients from the transposed image gT [L][NP][F], grid (tiles, binned levels). A (tile, bucket) run starts at the bucket's
+// base plus the tile's offset inside the bucket, both from the bucket scan: runs lie in a bucket in tile order (the consumer's
+// fixed-point sums do not depend on the order).
 // H: half-precision item stream (fp16 tables, F = 2): 8-byte pair items, 16-byte compact items.
 #ifdef SHACIRA_SCATTER_WAVES   // A/B builds: cap the registers so that this many waves share a SIMD
 #define SHACIRA_SCATTER_ATTR __attribute__((amdgpu_waves_per_eu(SHACIRA_SCATTER_WAVES)))
@@ -21,9 +21,8 @@ template <int DIM, int F, int FMT, bool STREAM = true>
 __global__ __launch_bounds__((ScatterThreads<DIM, F, FMT>::value)) SHACIRA_SCATTER_ATTR void bin_scatter_kernel(LevelTable lt, BinPlan plan,
                                                                   const float *__restrict__ coords,
                                                                   const float *__restrict__ gT,
-                                                                  unsigned long long *__restrict__ cursor,
-                                                                  const uint32_t *__restrict__ cnt, uint32_t cps,
-                                                                  uint32_t cnt_rows,
+                                                                  const uint64_t *__restrict__ base,
+                                                                  const uint32_t *__restrict__ run_off, uint32_t cps,
                                                                   typename ItemSel<F, FMT>::type *__restrict__ items,
                                                                   int64_t sample0, int64_t N, int64_t gpitch,
                                                                   float *__restrict__ zero_acc,
@@ -75,10 +74,12 @@ __global__ __launch_bounds__((ScatterThreads<DIM, F, FMT>::value)) SHACIRA_SCATT
     const bool compact = bl.compact != 0;   // (2-D: fp32 item stream only -- the plan never marks a level otherwise)
     constexpr uint32_t kCompactSlots = (DIM == 3) ? 2u : 1u;
     // every global load of the workgroup up front, unconditional (indices clamped into the batch): coordinates and
-    // gradients of the thread's samples, then -- waves 1 and 2 -- the tile's bucket counts (rows of cnt[tile][bucket]
-    // written by the counting pass) and straight away the returning atomic that reserves the bucket's run: it is the
-    // YOUNGEST memory operation of the wave, so nothing below waits for it until the run offsets are needed (after the
-    // staging phase); issued after the ranking instead, its round trip cost 23 us on S1
+    // gradients of the thread's samples, then -- waves 1 and 2 -- the bucket's base and the tile's offset inside the bucket
+    // (run_off[tile * cps][bucket]: the bucket scan left it in the first of the tile's cps counting rows), the YOUNGEST
+    // memory operations of the wave. They are added at once: the two waves wait for them where every wave waits for its
+    // coordinates anyway, a few instructions on. (Kept apart until the run's place is needed, after the staging phase, they
+    // cost a third register through the ranking -- 40 instead of 38 VGPRs in the 12-byte kernel -- and the S1 backward
+    // measured the same, 0.3915 against 0.3918 ms; profiles/scatter_prefix.md)
     float craw[SPT][DIM], graw[SPT][F];
 #pragma unroll
     for (int u = 0; u < SPT; ++u) {
@@ -101,20 +102,11 @@ __global__ __launch_bounds__((ScatterThreads<DIM, F, FMT>::value)) SHACIRA_SCATT
     // (round 5, tried and dropped: wave 1 laying out the tile's runs from the counting pass's numbers up front -- scan, pad fill
     // and final staging positions drawn by the ranking atomics themselves, two barriers and the scan phase fewer -- made this
     // kernel 75 us SLOWER on S1: every wave then waits behind one wave's global loads; profiles/r05_experiments.md)
-    const bool reserver = threadIdx.x >= 64 && threadIdx.x - 64 < bl.nb;
-    unsigned long long run_base = 0ull;
-    if (reserver) {
-        // cnt[counting tile][bucket] holds the ACTUAL numbers of item units; the run is reserved in multiples of plan.pad
+    const bool placer = threadIdx.x >= 64 && threadIdx.x - 64 < bl.nb;
+    uint64_t run_base = 0ull;
+    if (placer) {
         const uint32_t gb = bl.bucket0 + threadIdx.x - 64;
-        const uint32_t *row = cnt + (size_t)tile * cps * plan.total_buckets + gb;
-        uint32_t c = 0;
-        for (uint32_t k = 0; k < cps && tile * cps + k < cnt_rows; ++k) c += row[(size_t)k * plan.total_buckets];
-        c = (c + plan.pad - 1u) & ~(plan.pad - 1u);
-#ifdef ABL_NO_CURSOR   // ablation: no reservation (runs overlap: wrong results on purpose)
-        if (c) run_base = cursor[gb] + (unsigned long long)tile * c;
-#else
-        if (c) run_base = atomicAdd(&cursor[gb], (unsigned long long)c);
-#endif
+        run_base = base[gb] + run_off[(size_t)tile * cps * plan.total_buckets + gb];
     }
 #pragma unroll
     for (int u = 0; u < SPT; ++u) {
@@ -172,10 +164,10 @@ __global__ __launch_bounds__((ScatterThreads<DIM, F, FMT>::value)) SHACIRA_SCATT
             rank[u][q] = (ps[u][q].key >> 26) ? atomicAdd(&s_hist[ps[u][q].bucket], compact ? kCompactSlots : 1u) : 0u;
         }
     }
-    lds_barrier();   // (not __syncthreads(): its vmcnt(0) would wait for the reservation)
+    lds_barrier();
     if (threadIdx.x < 64) {  // wave 0: exclusive scan of the <= 128 bucket counts, two per lane
         const uint32_t lane = threadIdx.x;
-        // run lengths in multiples of plan.pad (line-aligned runs; what the reservation above took)
+        // run lengths in multiples of plan.pad (line-aligned runs; what the bucket scan laid out)
         const uint32_t pm = plan.pad - 1u;
         const uint32_t c0 = (2 * lane < bl.nb) ? ((s_hist[2 * lane] + pm) & ~pm) : 0u;
         const uint32_t c1 = (2 * lane + 1 < bl.nb) ? ((s_hist[2 * lane + 1] + pm) & ~pm) : 0u;
@@ -337,7 +329,7 @@ __global__ __launch_bounds__((ScatterThreads<DIM, F, FMT>::value)) SHACIRA_SCATT
         }
     }
     if (wi == 0) {
-        if (reserver) s_gbase[threadIdx.x - 64] = run_base;   // (waits for the reservation's return: the first use of it)
+        if (placer) s_gbase[threadIdx.x - 64] = run_base;
         __syncthreads();
     } else {
         lds_barrier();

@@ -8,11 +8,12 @@
 //
 //   pass F  front       grad_output [N, L*F] -> gT [L][NP][F] with 16-byte accesses both ways, FUSED with the bucket
 //                       counting of the same samples (front16_kernel): cnt[tile][bucket] rows + per-bucket totals
-//   pass S  scan        one workgroup: exclusive scan of the totals -> first item of every bucket, the cursors the
-//                       scatter pass reserves its runs from, and the consumer work list
-//   pass B  bin         recompute the corners, stage the tile's items in LDS sorted by bucket, reserve each (tile, bucket)
-//                       run with one returning atomic on the bucket's cursor, write it with coalesced 16-byte stores. Runs are
-//                       reserved in whole 64-byte pieces (round 5, BinPlan::pad: pad units = all-zero items): scattered runs
+//   pass S  scan        one launch. Workgroup 0: exclusive scan of the totals -> first item of every bucket and the consumer
+//                       work list. The others, 16 buckets each: prefix over the scatter tiles of the cnt columns -> the
+//                       offset of every (tile, bucket) run inside its bucket, left in place of the counts
+//   pass B  bin         recompute the corners, stage the tile's items in LDS sorted by bucket, load where each (tile, bucket)
+//                       run starts (bucket base + the tile's offset), write it with coalesced 16-byte stores. Runs are
+//                       whole 64-byte pieces long (round 5, BinPlan::pad: pad units = all-zero items): scattered runs
 //                       stream at 5.3 TB/s when they start and end on 64-byte boundaries, at 2.5-3.6 TB/s when they do not
 //   pass C  consume     persistent workgroups fetch (bucket, chunk) units: accumulate the items into an LDS-resident
 //                       64-bit fixed-point (or fp64) image of the bucket's rows, then write the rows out (plain coalesced
@@ -320,11 +321,11 @@ static void make_plan_uncached(int dim, int dtype, const LevelTable &lt, int64_t
     uint64_t chunk = (uint64_t)n_batch * plan.pairs / 48 + 1024;
     if (chunk < 8192) chunk = 8192;
     if (chunk > (1u << 22)) chunk = 1u << 22;
-    // Line-aligned runs (round 5). A (tile, bucket) run used to start wherever the bucket's cursor stood: every 128-byte line of
+    // Line-aligned runs (round 5). A (tile, bucket) run used to start right behind the one before it: every 128-byte line of
     // the item array was then written in two pieces by different 16-lane groups of a store (and the lines at a run's ends by
     // different workgroups), and scattered runs written that way reach 3.2 TB/s at 1 KB per run against 5.3 TB/s for the same
     // runs on line boundaries -- where the run LENGTH stops mattering at all (tools/microbench3.hip, profiles/r05_experiments.md).
-    // So runs are reserved in multiples of SHACIRA_RUN_ALIGN = 64 bytes (4 units of 16 bytes, or 16 units of 12 bytes = 192 bytes;
+    // So runs are multiples of SHACIRA_RUN_ALIGN = 64 bytes (4 units of 16 bytes, or 16 units of 12 bytes = 192 bytes;
     // pad units = all-zero items, which no consumer adds): large batches only
     // (below 2^17 samples the item array lives in the caches, which merge the pieces), 16-byte units only (a 24-byte unit would
     // need 192-byte multiples and goes through staging windows; the half-precision streams of fp16 tables -- 8-byte units, and
@@ -415,8 +416,8 @@ struct BinWorkspace {
     uint32_t *totals;             // [kTotalShards][kMaxBuckets] items per bucket (global atomics of the counting pass)
     uint32_t *gmax;               // [SHACIRA_MAX_LODS] bit patterns of max |grad_output| per level (right behind totals)
     uint64_t *base;
-    unsigned long long *cursor;   // [kMaxBuckets + 2] next free item slot of each bucket (scatter pass)
-    uint32_t *cnt;                // [tiles of the counting pass][total_buckets] items per (tile, bucket)
+    uint32_t *cnt;                // [tiles of the counting pass][total_buckets] items per (tile, bucket); behind the bucket scan
+                                  // a scatter tile's first row holds the offsets of its runs inside their buckets
     uint32_t *unit_first;
     UnitDesc *unit_desc;
     uint32_t *work_counter;       // next unit of the persistent consume pass (zeroed by the bucket scan)
@@ -511,7 +512,6 @@ static BinWorkspace carve(int dim, int dtype, const LevelTable &lt, int64_t n, v
     const uint64_t pad_units = (uint64_t)plan.num_tiles * plan.total_buckets * (plan.pad - 1u);
     const size_t o_items = take(((size_t)nb * slots_per_sample(plan) + (size_t)pad_units) * item);
     const size_t o_base = take((size_t)(kMaxBuckets + 2) * sizeof(uint64_t));
-    const size_t o_cur = take((size_t)(kMaxBuckets + 2) * sizeof(uint64_t));
     const size_t o_cnt = take((size_t)(nb / 128 + 8) * plan.total_buckets * sizeof(uint32_t));   // smallest counting tile: 128
     const size_t o_unit = take((size_t)(kMaxBuckets + 2) * sizeof(uint32_t));
     const uint64_t max_items_ws = (uint64_t)nb * plan.nbl * plan.pairs + pad_units;
@@ -526,7 +526,6 @@ static BinWorkspace carve(int dim, int dtype, const LevelTable &lt, int64_t n, v
         w.totals = reinterpret_cast<uint32_t *>(p + o_ctrl);
         w.gmax = w.totals + (size_t)kTotalShards * kMaxBuckets;
         w.base = reinterpret_cast<uint64_t *>(p + o_base);
-        w.cursor = reinterpret_cast<unsigned long long *>(p + o_cur);
         w.cnt = reinterpret_cast<uint32_t *>(p + o_cnt);
         w.unit_first = reinterpret_cast<uint32_t *>(p + o_unit);
         w.unit_desc = reinterpret_cast<UnitDesc *>(p + o_ub);
@@ -894,13 +893,16 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
             SHACIRA_CHECK_LAUNCH();
         }
         first_batch = false;
-        hipLaunchKernelGGL(bin_scan_buckets_kernel, dim3(1), dim3(1024), 0, s, w.totals, w.base, w.unit_first, w.unit_desc,
-                           plan.total_buckets, plan, w.work_counter, w.cursor, use_fx ? w.gmax : nullptr);
+        // counting rows per scatter tile (the fused front kernel counts in tiles of ts16 samples) and in all
+        const uint32_t cps = fused_now ? (uint32_t)(TileOf<DIM>::value / ts16) : 1u;
+        const uint32_t cnt_rows = fused_now ? (uint32_t)((n + ts16 - 1) / ts16) : plan.num_tiles;
+        static_assert(TileOf<DIM>::value / 128 <= kScanRows, "a thread of the bucket scan walks whole scatter tiles");
+        hipLaunchKernelGGL(bin_scan_buckets_kernel, dim3(1u + (plan.total_buckets + kScanCols - 1u) / kScanCols),
+                           dim3(kScanThreads), 0, s, w.totals, w.base, w.unit_first, w.unit_desc, plan.total_buckets, plan,
+                           w.work_counter, use_fx ? w.gmax : nullptr, w.cnt, cps, cnt_rows);
         SHACIRA_CHECK_LAUNCH();
         // (selective zeroing: hashed buckets with 0 or several units are zeroed by the scatter pass's tail)
         float *zacc = selective ? acc : nullptr;
-        const uint32_t cps = fused_now ? (uint32_t)(TileOf<DIM>::value / ts16) : 1u;
-        const uint32_t cnt_rows = fused_now ? (uint32_t)((n + ts16 - 1) / ts16) : plan.num_tiles;
         bool fork_signalled = false;   // the scatter launch itself signals the brick pass's fork event (below)
         if (fmt == 2) {
             if constexpr (DIM == 3 && F == 2) {
@@ -913,28 +915,28 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
                     cap == hipStreamCaptureStatusNone) {
                     hipExtLaunchKernelGGL((bin_scatter_kernel<DIM, F, 2>), SCATTER_GRID(plan),
                                           dim3(ScatterThreads<DIM, F, 2>::value), (uint32_t)stage_bytes(plan), s, nullptr,
-                                          bss->bfork, 0u, lt, plan, cptr, (const float *)w.gT, w.cursor, (const uint32_t *)w.cnt, cps, cnt_rows,
+                                          bss->bfork, 0u, lt, plan, cptr, (const float *)w.gT, (const uint64_t *)w.base, (const uint32_t *)w.cnt, cps,
                                           reinterpret_cast<Item12 *>(w.items), s0, hi, NP, zacc, first_idx,
                                           (const uint32_t *)w.unit_first, cstride);
                     fork_signalled = true;
                 } else {
                     hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, 2>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 2>::value),
-                                       stage_bytes(plan), s, lt, plan, cptr, w.gT, w.cursor, w.cnt, cps, cnt_rows,
+                                       stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
                                        reinterpret_cast<Item12 *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
                 }
             }
         } else if (half)
             hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, true>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 1>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.cursor, w.cnt, cps, cnt_rows,
+                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
                                reinterpret_cast<typename ItemSel<F, true>::type *>(w.items), s0, hi, NP, zacc, first_idx,
                                w.unit_first, cstride);
         else if (use_fx)
             hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, false>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 0>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.cursor, w.cnt, cps, cnt_rows,
+                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
                                reinterpret_cast<Item<F> *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
         else   // batches below 2^17 samples: plain item stores, the consume pass reads them back from the caches
             hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, false, false>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 0>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.cursor, w.cnt, cps, cnt_rows,
+                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
                                reinterpret_cast<Item<F> *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
         SHACIRA_CHECK_LAUNCH();
         if (fork) SHACIRA_CHECK(hipStreamWaitEvent(s, ss->join, 0));   // table zeroed, direct levels in
