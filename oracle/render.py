@@ -66,6 +66,31 @@ def exponential_integration(feats, tau, boundary, exclusive=True):
     return sum_reduce(transmittance * feats, boundary), transmittance
 
 
+def exponential_integration_packed(feats, tau, pack_start):
+    """`exponential_integration` (exclusive) over per-pack offsets int64 [R + 1] instead of boundary flags: a pack may be
+    empty (repeated offsets -> a zero ray row), and rows outside [pack_start[0], pack_start[-1]) belong to no pack (weight
+    0) -- the forms the marcher's `ray_offsets` and its capped emit hand over, which flags cannot express. Every pack is
+    summed on its own and the exclusive prefix is the inclusive one shifted by a sample, so a non-finite tau stays inside
+    its pack and an infinite one gives weight T at that sample and 0 behind it."""
+    ps = [int(v) for v in pack_start]
+    rays, w = [], [torch.zeros(ps[0], 1, dtype=torch.float64)]
+    for b, e in zip(ps[:-1], ps[1:]):
+        t, f = tau[b:e].double().reshape(-1, 1), feats[b:e].double()
+        incl = torch.cumsum(t, 0)
+        excl = torch.cat([torch.zeros(min(1, e - b), 1, dtype=torch.float64), incl[:-1]])
+        wp = torch.exp(-excl) * (1.0 - torch.exp(-t))
+        rays.append((wp * f).sum(0))
+        w.append(wp)
+    w.append(torch.zeros(feats.shape[0] - ps[-1], 1, dtype=torch.float64))
+    return torch.stack(rays) if rays else torch.zeros(0, feats.shape[1], dtype=torch.float64), torch.cat(w)
+
+
+def sum_reduce_packed(x, pack_start):
+    """`sum_reduce` over per-pack offsets (empty packs give zero rows, rows no pack covers are not summed)."""
+    ps = [int(v) for v in pack_start]
+    return torch.stack([x[b:e].double().sum(0) for b, e in zip(ps[:-1], ps[1:])])
+
+
 def quantize_points(x, level):
     res = 2 ** level
     return torch.floor(torch.clamp(res * (x + 1.0) / 2.0, 0, res - 1.0)).long()

@@ -26,38 +26,39 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float *__restrict__ p, f
         lr_over_bc1 = (float)((double)lr / (1.0 - pow((double)b1, t)));
         inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
     }
+    // float4 accesses need all four pointers on 16 bytes; a view into a flat buffer (dist.FlatGradients) is only 4-byte
+    // aligned, and then every element goes through the scalar loop (as in adam_multi_kernel)
+    const bool aligned = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+    const int64_t n4 = aligned ? (n & ~(int64_t)3) : 0;   // elements stepped as float4 groups
     const int64_t stride = (int64_t)gridDim.x * 256 * 4;
-    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
-        if (i + 4 <= n) {
-            float4 pp = *reinterpret_cast<float4 *>(p + i);
-            float4 gg = *reinterpret_cast<float4 *>(g + i);
-            float4 mm = *reinterpret_cast<float4 *>(m + i);
-            float4 vv = *reinterpret_cast<float4 *>(v + i);
-            float *pa = &pp.x, *ga = &gg.x, *ma = &mm.x, *va = &vv.x;
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n4; i += stride) {
+        float4 pp = *reinterpret_cast<float4 *>(p + i);
+        float4 gg = *reinterpret_cast<float4 *>(g + i);
+        float4 mm = *reinterpret_cast<float4 *>(m + i);
+        float4 vv = *reinterpret_cast<float4 *>(v + i);
+        float *pa = &pp.x, *ga = &gg.x, *ma = &mm.x, *va = &vv.x;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float gr = ga[k] + wd * pa[k];
-                ma[k] = b1 * ma[k] + (1.0f - b1) * gr;
-                va[k] = b2 * va[k] + (1.0f - b2) * gr * gr;
-                const float denom = sqrtf(va[k]) * inv_sqrt_bc2 + eps;
-                pa[k] = pa[k] - lr_over_bc1 * (ma[k] / denom);
-            }
-            *reinterpret_cast<float4 *>(p + i) = pp;
-            *reinterpret_cast<float4 *>(m + i) = mm;
-            *reinterpret_cast<float4 *>(v + i) = vv;
-            if (zero_grad) *reinterpret_cast<float4 *>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            for (int64_t j = i; j < n; ++j) {
-                const float gr = g[j] + wd * p[j];
-                const float mj = b1 * m[j] + (1.0f - b1) * gr;
-                const float vj = b2 * v[j] + (1.0f - b2) * gr * gr;
-                const float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
-                p[j] = p[j] - lr_over_bc1 * (mj / denom);
-                m[j] = mj;
-                v[j] = vj;
-                if (zero_grad) g[j] = 0.0f;
-            }
+        for (int k = 0; k < 4; ++k) {
+            const float gr = ga[k] + wd * pa[k];
+            ma[k] = b1 * ma[k] + (1.0f - b1) * gr;
+            va[k] = b2 * va[k] + (1.0f - b2) * gr * gr;
+            const float denom = sqrtf(va[k]) * inv_sqrt_bc2 + eps;
+            pa[k] = pa[k] - lr_over_bc1 * (ma[k] / denom);
         }
+        *reinterpret_cast<float4 *>(p + i) = pp;
+        *reinterpret_cast<float4 *>(m + i) = mm;
+        *reinterpret_cast<float4 *>(v + i) = vv;
+        if (zero_grad) *reinterpret_cast<float4 *>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int64_t j = n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+        const float gr = g[j] + wd * p[j];
+        const float mj = b1 * m[j] + (1.0f - b1) * gr;
+        const float vj = b2 * v[j] + (1.0f - b2) * gr * gr;
+        const float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
+        p[j] = p[j] - lr_over_bc1 * (mj / denom);
+        m[j] = mj;
+        v[j] = vj;
+        if (zero_grad) g[j] = 0.0f;
     }
 }
 

@@ -30,6 +30,17 @@ __device__ __forceinline__ float wave_incl_scan_rev(float v, int lane) {   // su
     }
     return v;
 }
+// The exclusive sums are the neighbour lane's inclusive sum, never `incl - v`: when one sample dwarfs the ones before it
+// (an opaque sample behind thin ones) the subtraction reads the small prefix back out of a sum whose ulp is as large as the
+// prefix itself, and with v = inf it is inf - inf.
+__device__ __forceinline__ float wave_excl_from_incl(float incl, int lane) {
+    const float n = __shfl_up(incl, 1, 64);
+    return lane == 0 ? 0.0f : n;
+}
+__device__ __forceinline__ float wave_excl_from_incl_rev(float incl_rev, int lane) {   // lane i gets sum_{k > i}
+    const float n = __shfl_down(incl_rev, 1, 64);
+    return lane == 63 ? 0.0f : n;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -58,7 +69,7 @@ __global__ __launch_bounds__(64 * kPackWaves) void pack_integrate_fwd_kernel(con
         const bool live = i < end;
         const float t = live ? tau[i] : 0.0f;
         const float incl = wave_incl_scan(t, lane);
-        const float excl = carry + (incl - t);
+        const float excl = carry + wave_excl_from_incl(incl, lane);
         const float w = live ? expf(-excl) * (1.0f - expf(-t)) : 0.0f;
         if (live) {
             weights[i] = w;
@@ -100,7 +111,8 @@ __global__ __launch_bounds__(64 * kPackWaves) void pack_integrate_bwd_kernel(
         const bool live = i < end;
         const float t = live ? tau[i] : 0.0f;
         const float incl = wave_incl_scan(t, lane);
-        if (live) g_tau[i] = carry + (incl - t);
+        const float excl = carry + wave_excl_from_incl(incl, lane);
+        if (live) g_tau[i] = excl;
         carry += __shfl(incl, 63, 64);
     }
     const int64_t nchunks = (end - begin + 63) / 64;
@@ -126,7 +138,8 @@ __global__ __launch_bounds__(64 * kPackWaves) void pack_integrate_bwd_kernel(
             e_term = G * T * et;
         }
         const float incl_rev = wave_incl_scan_rev(gw_term, lane);   // sum_{k >= i} within the chunk
-        if (live) g_tau[i] = e_term - (suffix + (incl_rev - gw_term));
+        const float after = wave_excl_from_incl_rev(incl_rev, lane);   // sum_{k > i} within the chunk
+        if (live) g_tau[i] = e_term - (suffix + after);
         suffix += __shfl(incl_rev, 0, 64);
     }
 }

@@ -37,7 +37,7 @@ class _ExponentialIntegration(torch.autograd.Function):
         S, C = feats.shape
         R = pack_start.shape[0] - 1
         ray_feats = torch.empty((R, C), dtype=torch.float32, device=feats.device)
-        weights = torch.empty((S,), dtype=torch.float32, device=feats.device)
+        weights = torch.zeros((S,), dtype=torch.float32, device=feats.device)   # rows no pack covers (capped emit): 0
         with _on_device(feats.device):
             _lib.check(_lib.lib().shacira_pack_integrate_forward(S, R, C, _ptr(feats), _ptr(tau), _ptr(pack_start),
                                                                  _ptr(ray_feats), _ptr(weights), _stream(feats)),

@@ -110,3 +110,51 @@ def test_capturable_counter_splits_when_a_sharer_is_skipped():
     for x, y in zip(pa, pb):
         torch.testing.assert_close(x, y, rtol=2e-6, atol=1e-7)
     assert int(ob.state[pb[0]]["step"].item()) == 6 and int(ob.state[pb[1]]["step"].item()) == 4
+
+
+@pytest.mark.parametrize("wd", [0.0, 0.01])
+def test_adam_ref_equals_torch_adam_on_double_parameters(wd):
+    """tests/adam_ref.py (the fp64 yardstick of the GPU edge tests) against torch.optim.Adam on DOUBLE parameters, ten steps from
+    zero state, both given the hyper-parameters as the fp32 values the C-ABI carries. They differ in one place only: the
+    reference rounds lr / (1 - b1^t) and 1 / sqrt(1 - b2^t) to fp32 as the kernels do, 2^-24 relative each, so every step may
+    move p by 2^-23 of its update (asserted with 2^-22, summed over the steps); the moments see that only through wd * p."""
+    import numpy as np
+    import adam_ref
+    rng = np.random.default_rng(7)
+    n, lr, b1, b2, eps = 257, 0.02, 0.9, 0.999, 1e-8
+    f32 = lambda x: float(np.float32(x))
+    p = rng.standard_normal(n) * 0.1
+    tp = torch.nn.Parameter(torch.from_numpy(p.copy()))
+    opt = torch.optim.Adam([tp], lr=f32(lr), betas=(f32(b1), f32(b2)), eps=f32(eps), weight_decay=f32(wd), foreach=False)
+    m, v, slack = np.zeros(n), np.zeros(n), np.zeros(n)
+    for t in range(1, 11):
+        g = rng.standard_normal(n)
+        tp.grad = torch.from_numpy(g.copy())
+        opt.step()
+        p_new, m, v, scale = adam_ref.adam_step(p, g, m, v, t, lr=lr, b1=b1, b2=b2, eps=eps, wd=wd)
+        slack += 2.0 ** -22 * np.abs(p - p_new)
+        p = p_new
+        assert np.all(np.abs(tp.detach().numpy() - p) <= slack + 1e-15), t
+    st = opt.state[tp]
+    # the moments see p only through g' = g + wd p: |dm| <= wd |dp|, |dv| <= 2 |g'| wd |dp| with |g'| < 6 here
+    np.testing.assert_allclose(st["exp_avg"].numpy(), m, rtol=1e-12, atol=wd * slack.max() + 1e-15)
+    np.testing.assert_allclose(st["exp_avg_sq"].numpy(), v, rtol=1e-12, atol=12 * wd * slack.max() + 1e-15)
+
+
+def test_adam_ref_single_step_yardstick_is_tight():
+    """The update allowance of the GPU edge tests is four times what CPU torch fp32 Adam misses adam_ref by on the same inputs,
+    in units of the update's size before exp_avg's two terms cancel. That figure is a handful of fp32 roundings (measured:
+    2.5e-7 to 3.0e-7 on 4M random elements, i.e. under 6 * 2^-24), so the bar stays near 1e-6 of an update."""
+    import numpy as np
+    import adam_ref
+    rng = np.random.default_rng(0)
+    n = 20000
+    p, g = (rng.standard_normal(n) * 0.1).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    m, v = (rng.standard_normal(n) * 0.1).astype(np.float32), (rng.random(n) * 0.01).astype(np.float32)
+    for t, wd in ((1, 0.0), (7, 0.01), (10 ** 6, 0.01)):
+        allowance, measured = adam_ref.update_allowance(p, g, m, v, t, lr=0.02, b1=0.9, b2=0.999, eps=1e-8, wd=wd)
+        assert 0 < measured < 8 * 2.0 ** -24 and allowance == max(4 * measured, 2.0 ** -21), (t, wd, measured)
+        got = adam_ref.torch_single_step(p, g, m, v, t, lr=0.02, b1=0.9, b2=0.999, eps=1e-8, wd=wd)
+        p_ref, m_ref, v_ref, scale = adam_ref.adam_step(p, g, m, v, t, lr=0.02, b1=0.9, b2=0.999, eps=1e-8, wd=wd)
+        assert np.all(scale >= np.abs(p.astype(np.float64) - p_ref) * (1 - 1e-12))
+        assert np.abs(got - p_ref).max() < 1e-6
