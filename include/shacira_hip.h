@@ -628,6 +628,13 @@ SHACIRA_API int shacira_entropy_bits_backward(int64_t num_rows, int latent_dim, 
  *   x [num_rows, in_dim], y / grad_y [num_rows, out_dim], grad_x [num_rows, in_dim] (may be NULL)
  * Only a fixed set of shapes is compiled (shacira_mlp_supported); others return SHACIRA_EDTYPE and the caller keeps
  * using its own Linear layers. The backward recomputes the hidden activations (nothing is saved by the forward).
+ * (Behaviour tightened within ABI 11, no signature change: the alignment refusal below is new -- such pointers were launched
+ * on before -- and so is the NaN rule; a caller that passed aligned, finite operands sees the same results to fp32 rounding.)
+ * Alignment: rows of 4n floats are moved as 16-byte vectors, so x and grad_x must be 16-byte aligned when in_dim % 4 == 0
+ * and y when out_dim % 4 == 0; otherwise SHACIRA_EINVAL and nothing runs. params, grad_y, grad_params need 4 bytes only.
+ * Non-finite values: the ReLU is torch.relu's -- a NaN pre-activation gives a NaN activation, and a NaN activation passes
+ * its upstream gradient on (only h <= 0 blocks it) -- so a row with a NaN feature has a NaN output row.
+ * num_rows == 0: the forward does nothing; the backward writes grad_params = 0 (x, grad_y, grad_x may be NULL).
  */
 SHACIRA_API int shacira_mlp_supported(int in_dim, int hidden_dim, int num_hidden, int out_dim);
 SHACIRA_API size_t shacira_mlp_backward_workspace_bytes(int in_dim, int hidden_dim, int num_hidden, int out_dim);

@@ -1103,6 +1103,11 @@ size_t shacira_mlp_backward_workspace_bytes(int in_dim, int hidden_dim, int num_
                ? mlp_workspace_bytes(in_dim, hidden_dim, num_hidden, out_dim) : 0;
 }
 
+// rows of 4n floats are read and written as float4 (mlp.hip load_row_in, mlp_mfma.hip load_input / store_rows)
+static bool mlp_row_pointer_ok(const void *p, int row_floats) {
+    return row_floats % 4 != 0 || (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
 int shacira_mlp_forward(int64_t num_rows, int in_dim, int hidden_dim, int num_hidden, int out_dim, const float *x,
                         const float *params, float *y, void *stream) {
     options_snapshot();
@@ -1110,6 +1115,7 @@ int shacira_mlp_forward(int64_t num_rows, int in_dim, int hidden_dim, int num_hi
     if (!mlp_supported(in_dim, hidden_dim, num_hidden, out_dim)) return SHACIRA_EDTYPE;
     if (num_rows == 0) return 0;
     if (!x || !params || !y) return SHACIRA_EINVAL;
+    if (!mlp_row_pointer_ok(x, in_dim) || !mlp_row_pointer_ok(y, out_dim)) return SHACIRA_EINVAL;
     return (int)mlp_dispatch(false, in_dim, hidden_dim, num_hidden, out_dim, num_rows, x, params, y, nullptr, nullptr,
                              nullptr, nullptr, (hipStream_t)stream);
 }
@@ -1123,6 +1129,7 @@ int shacira_mlp_backward(int64_t num_rows, int in_dim, int hidden_dim, int num_h
     if (!workspace || workspace_bytes < mlp_workspace_bytes(in_dim, hidden_dim, num_hidden, out_dim))
         return SHACIRA_EWORKSPACE;
     if (!params || !grad_params || (num_rows > 0 && (!x || !grad_y))) return SHACIRA_EINVAL;
+    if (num_rows > 0 && (!mlp_row_pointer_ok(x, in_dim) || !mlp_row_pointer_ok(grad_x, in_dim))) return SHACIRA_EINVAL;
     return (int)mlp_dispatch(true, in_dim, hidden_dim, num_hidden, out_dim, num_rows, x, params, nullptr, grad_y,
                              grad_x, grad_params, static_cast<double *>(workspace), (hipStream_t)stream);
 }

@@ -293,4 +293,9 @@ const Options &opt();             // the calling thread's snapshot
 void options_snapshot();          // taken at every extern "C" entry point that reads options
 void options_resolve_item12(int value);   // a call's decision for the automatic setting (-1), into the calling thread's snapshot
 
+// The decoder MLP's ReLU (mlp.hip, mlp_mfma.hip) as torch.relu has it: a NaN stays a NaN (fmaxf returns the other operand).
+// llvm.maximum is IEEE 754-2019 maximum, one v_maximum3_f32 on gfx950; the select "z < 0 ? 0 : z" means the same but made the
+// VALU forward kernels spill 400-850 bytes per lane.
+__device__ __forceinline__ float relu_keep_nan(float z) { return __builtin_elementwise_maximum(z, 0.0f); }
+
 }  // namespace shacira

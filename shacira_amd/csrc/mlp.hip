@@ -55,7 +55,7 @@ __device__ __forceinline__ void mlp_forward_regs(const float *__restrict__ sw, c
 #pragma unroll
                 for (int i = 0; i < H; ++i) acc = fmaf(h[l - 1][i], W[j * H + i], acc);
             }
-            h[l][j] = fmaxf(acc, 0.0f);
+            h[l][j] = relu_keep_nan(acc);
         }
     }
     const float *Wo = sw + S::w_off(NH);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kMlpTile) void mlp_backward_kernel(const float *__r
                 float a = 0.0f;
 #pragma unroll
                 for (int o = 0; o < OUT; ++o) a = fmaf(Wo[o * H + i], d[o], a);
-                dh[i] = (h[NH - 1][i] > 0.0f) ? a : 0.0f;  // through the ReLU: gradient of the pre-activation
+                dh[i] = (h[NH - 1][i] <= 0.0f) ? 0.0f : a;  // through the ReLU (a NaN activation lets its gradient through)
             }
         }
 #pragma unroll
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kMlpTile) void mlp_backward_kernel(const float *__r
                     float a = 0.0f;
 #pragma unroll
                     for (int j = 0; j < H; ++j) a = fmaf(W[j * H + i], dh[j], a);
-                    dn[i] = (h[l - 1][i] > 0.0f) ? a : 0.0f;
+                    dn[i] = (h[l - 1][i] <= 0.0f) ? 0.0f : a;
                 }
 #pragma unroll
                 for (int i = 0; i < H; ++i) dh[i] = dn[i];

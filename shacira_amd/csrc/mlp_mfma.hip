@@ -18,7 +18,9 @@
 // Weight gradients contract over SAMPLES (dW = dZ^T . In), which needs both operands with the lane on the other
 // index: the wave stages dZ^T and In through a private LDS region per layer (bank-conflict-free pitches), MB/NQ MFMA
 // steps per block of dW, accumulators persistent across the wave's tiles; bias gradients fall out of the same LDS reads.
-// Block partials in fp64 + the finishing kernel of mlp.hip (reproducible for a fixed grid).
+// Block partials in fp64 + the finishing kernel of mlp.hip. Every sum has a fixed order: a wave's tiles in grid-stride
+// order, the workgroup's four waves in wave order (they take turns at the block image), the blocks in the finishing
+// kernel's tree -- so for a given batch size (which fixes the grid) the weight gradients are bit-for-bit reproducible.
 #include <mutex>
 
 #include "internal.h"
@@ -47,6 +49,7 @@ template <> struct Mma<16> {
         return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
     }
 };
+
 template <int MB> __device__ __forceinline__ constexpr int crow(int v, int q) {
     return (v >> 2) * (4 * Mma<MB>::NQ) + 4 * q + (v & 3);
 }
@@ -98,7 +101,7 @@ template <class S, int NH> __device__ __forceinline__ void load_weights(float *s
     __syncthreads();
 }
 
-// out^T[ob] = W[MB*ob.., :] . in^T + b   (A = W rows from LDS as float4 over 4 consecutive k, B = in[b][v])
+// out^T[ob] = (W[MB*ob.., :] . in^T) + b   (A = W rows from LDS as float4 over 4 consecutive k, B = in[b][v])
 template <int MB, int KB, int OB, bool RELU>
 __device__ __forceinline__ void layer_forward(const float *__restrict__ sW, int pitch, const float *__restrict__ sB,
                                               const typename Mma<MB>::acc_t (&in)[KB],
@@ -108,7 +111,7 @@ __device__ __forceinline__ void layer_forward(const float *__restrict__ sW, int 
     for (int ob = 0; ob < OB; ++ob) {
         typename M::acc_t acc;
 #pragma unroll
-        for (int v = 0; v < M::NA; ++v) acc[v] = sB[MB * ob + crow<MB>(v, q)];
+        for (int v = 0; v < M::NA; ++v) acc[v] = 0.0f;
 #pragma unroll
         for (int b = 0; b < KB; ++b) {
 #pragma unroll
@@ -121,9 +124,13 @@ __device__ __forceinline__ void layer_forward(const float *__restrict__ sW, int 
                 acc = M::mma(a.w, in[b][4 * g + 3], acc);
             }
         }
+        // the bias goes in last (as the accumulator's start value every one of the fan-in roundings would happen at the size of
+        // the bias: with features of 1e-4, |W x| << |b|, the activation was off by sqrt(fan_in) ulps of b)
+#pragma unroll
+        for (int v = 0; v < M::NA; ++v) acc[v] += sB[MB * ob + crow<MB>(v, q)];
         if (RELU) {
 #pragma unroll
-            for (int v = 0; v < M::NA; ++v) acc[v] = fmaxf(acc[v], 0.0f);
+            for (int v = 0; v < M::NA; ++v) acc[v] = relu_keep_nan(acc[v]);
         }
         out[ob] = acc;
         // width 128: keep the scheduler from hoisting every block's LDS operand loads to the top (spills at 512 registers)
@@ -271,7 +278,8 @@ __device__ __forceinline__ void stage_dz(float *s_dz, const typename Mma<MB>::ac
         for (int v = 0; v < Mma<MB>::NA; ++v) s_dz[(MB * b + crow<MB>(v, q)) * (MB + 1) + j] = t[b][v];
 }
 
-// dW block -> the block's fp32 parameter-gradient image in LDS
+// dW block -> the block's fp32 parameter-gradient image in LDS. Called by ONE wave at a time (the waves take turns, see the
+// kernel): every weight element has exactly one lane of the wave, so these are plain adds in a fixed order.
 template <int MB, int KB, int OB>
 __device__ __forceinline__ void flush_dw(float *s_gp, int p_off, int fan_in, int fan_out,
                                          const typename Mma<MB>::acc_t (&dw)[OB][KB], const float (&db)[OB], int j, int q) {
@@ -282,12 +290,16 @@ __device__ __forceinline__ void flush_dw(float *s_gp, int p_off, int fan_in, int
 #pragma unroll
             for (int v = 0; v < Mma<MB>::NA; ++v) {
                 const int o = MB * ob + crow<MB>(v, q), k = MB * kb + j;
-                if (o < fan_out && k < fan_in) atomicAdd(&s_gp[p_off + o * fan_in + k], dw[ob][kb][v]);
+                if (o < fan_out && k < fan_in) s_gp[p_off + o * fan_in + k] += dw[ob][kb][v];
             }
         }
-        // bias: lane (i, q) holds the sum over its MB / NQ samples of row MB*ob + i
+        // bias: lane (j, q) holds the sum over its MB / NQ samples of row MB*ob + j: add the NQ lanes of the row (butterfly:
+        // the same value in every lane whatever the order), lane q == 0 adds it to the image
+        float t = db[ob];
+#pragma unroll
+        for (int m = MB; m < 64; m <<= 1) t += __shfl_xor(t, m, 64);
         const int o = MB * ob + j;
-        if (o < fan_out) atomicAdd(&s_gp[p_off + fan_in * fan_out + o], db[ob]);
+        if (q == 0 && o < fan_out) s_gp[p_off + fan_in * fan_out + o] += t;
     }
 }
 
@@ -355,7 +367,7 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void wide_mlp_backward_kernel(
 #pragma unroll
         for (int b = 0; b < S::HB; ++b)
 #pragma unroll
-            for (int v = 0; v < M::NA; ++v) dcur[b][v] = (hlast[b][v] > 0.0f) ? dcur[b][v] : 0.0f;
+            for (int v = 0; v < M::NA; ++v) dcur[b][v] = (hlast[b][v] <= 0.0f) ? 0.0f : dcur[b][v];
         if constexpr (NH == 2) {
             // hidden layer 1: dW_1 = dZ_1^T . H_0, then dH_0
             stage_in<MB, S::HB>(s_in, S::stage_in_pitch, h0, i, q);
@@ -368,7 +380,7 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void wide_mlp_backward_kernel(
 #pragma unroll
             for (int b = 0; b < S::HB; ++b)
 #pragma unroll
-                for (int v = 0; v < M::NA; ++v) dcur[b][v] = (h0[b][v] > 0.0f) ? dprev[b][v] : 0.0f;
+                for (int v = 0; v < M::NA; ++v) dcur[b][v] = (h0[b][v] <= 0.0f) ? 0.0f : dprev[b][v];
         }
         // first layer: dW_0 = dZ_0^T . X, then dX
         stage_in<MB, S::KB0>(s_in, S::stage_in_pitch, in0, i, q);
@@ -382,11 +394,17 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void wide_mlp_backward_kernel(
             store_rows<MB, IN, S::KB0>(gx, s, live, dx, q);
         }
     }
-    // wave accumulators -> block image (LDS float atomics: once per kernel) -> fp64 block partial
-    flush_dw<MB, S::KB0, S::HB>(s_gp, S::p_off(0), IN, H, dw0, db0, i, q);
-    if constexpr (NH == 2) flush_dw<MB, S::HB, S::HB>(s_gp, S::p_off(1), H, H, dw1, db1, i, q);
-    flush_dw<MB, S::HB, 1>(s_gp, S::p_off(NH), H, OUT, dwo, dbo, i, q);
-    __syncthreads();
+    // wave accumulators -> block image -> fp64 block partial. The four waves add in wave order, a barrier between turns (once
+    // per kernel): the fp32 sum of the image does not depend on which wave arrives first.
+#pragma unroll 1
+    for (int tw = 0; tw < kMfmaWaves; ++tw) {
+        if (wave == tw) {
+            flush_dw<MB, S::KB0, S::HB>(s_gp, S::p_off(0), IN, H, dw0, db0, i, q);
+            if constexpr (NH == 2) flush_dw<MB, S::HB, S::HB>(s_gp, S::p_off(1), H, H, dw1, db1, i, q);
+            flush_dw<MB, S::HB, 1>(s_gp, S::p_off(NH), H, OUT, dwo, dbo, i, q);
+        }
+        __syncthreads();
+    }
     for (int e = threadIdx.x; e < S::n_params; e += 64 * kMfmaWaves)
         partials[(size_t)blockIdx.x * S::n_params + e] = (double)s_gp[e];
 }
@@ -483,7 +501,7 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void split_mlp_backward_kernel(
 #pragma unroll
         for (int b = 0; b < S::HB; ++b)
 #pragma unroll
-            for (int v = 0; v < M::NA; ++v) dcur[b][v] = (hlast[b][v] > 0.0f) ? dcur[b][v] : 0.0f;
+            for (int v = 0; v < M::NA; ++v) dcur[b][v] = (hlast[b][v] <= 0.0f) ? 0.0f : dcur[b][v];
         if constexpr (NH == 2) {
 #pragma unroll 1
             for (int tw = 0; tw < kMfmaWaves; ++tw) {
@@ -500,7 +518,7 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void split_mlp_backward_kernel(
 #pragma unroll
             for (int b = 0; b < S::HB; ++b)
 #pragma unroll
-                for (int v = 0; v < M::NA; ++v) dcur[b][v] = (h0[b][v] > 0.0f) ? dprev[b][v] : 0.0f;
+                for (int v = 0; v < M::NA; ++v) dcur[b][v] = (h0[b][v] <= 0.0f) ? 0.0f : dprev[b][v];
         }
         // two hidden layers: the inputs are read again here instead of being kept in 32 registers through both chains
         // (the compiler spilled 216 B / lane otherwise); x2 is opaque so that the two reads are not merged

@@ -718,8 +718,17 @@ def mlp_supported(in_dim, hidden_dim, num_hidden, out_dim):
     return bool(_lib.lib().shacira_mlp_supported(int(in_dim), int(hidden_dim), int(num_hidden), int(out_dim)))
 
 
+def _mlp_rows(x, in_dim):
+    """The kernels move rows of 4n floats as 16-byte vectors (the C-ABI refuses a pointer that is not 16-byte aligned then): a
+    view that starts elsewhere, as a slice of a flat buffer does, is copied into an allocation of its own."""
+    if in_dim % 4 == 0 and x.data_ptr() % 16 != 0:
+        return x.clone(memory_format=torch.contiguous_format)
+    return x
+
+
 def mlp_forward(x, params, in_dim, hidden_dim, num_hidden, out_dim):
     _need_gpu(x, params)
+    x = _mlp_rows(x, in_dim)
     y = torch.empty((x.shape[0], out_dim), dtype=torch.float32, device=x.device)
     with _on_device(x.device):
         rc = _lib.lib().shacira_mlp_forward(x.shape[0], in_dim, hidden_dim, num_hidden, out_dim, _ptr(x), _ptr(params),
@@ -731,8 +740,9 @@ def mlp_forward(x, params, in_dim, hidden_dim, num_hidden, out_dim):
 def mlp_backward(x, params, grad_y, in_dim, hidden_dim, num_hidden, out_dim, need_grad_x=True):
     _need_gpu(x, params, grad_y)
     dev = x.device
-    gx = torch.empty_like(x) if need_grad_x else None
-    gp = torch.empty_like(params)
+    x = _mlp_rows(x, in_dim)
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_grad_x else None
+    gp = torch.empty(params.shape, dtype=torch.float32, device=dev)
     L = _lib.lib()
     with _on_device(dev):
         n = L.shacira_mlp_backward_workspace_bytes(in_dim, hidden_dim, num_hidden, out_dim)
