@@ -563,6 +563,69 @@ SHACIRA_API int shacira_mesh_voxelize(int64_t num_triangles, const float *triang
                                       size_t workspace_bytes, void *stream);
 
 /*
+ * Structural similarity (SSIM) of a prediction x against a target y, and its gradient with respect to x: what
+ * skimage.metrics.structural_similarity(x, y, data_range=R, gaussian_weights=True, sigma=1.5, channel_axis=2) computes, the
+ * second number the reference reports per validation image (wisp/ops/image/metrics.py:111-132).
+ *   x, y          [H, W, pixel_stride] fp32, channels last; the first `channels` floats of every pixel are read. A
+ *                 pixel_stride above `channels` lets the RGB of an RGBA buffer through without a copy
+ *   data_range    R, fp32, finite, > 0
+ *   value         out, ONE fp64: the SSIM (overwritten)
+ *   map           out, may be NULL: fp32 [H, W, channels], the score of every pixel (overwritten)
+ *   grad          backward: ONE fp32 on the device, dL/d(value)
+ *   grad_x        backward out: fp32 [H, W, pixel_stride] (overwritten; channels >= `channels` receive exactly zero).
+ *                 There is no gradient with respect to y.
+ *
+ * Per channel, on the planes x, y:
+ *   window   w[k] = exp(-0.5 (k / 1.5)^2), k = -5 .. 5, divided by their sum in fp64, then rounded to fp32; G = the window along
+ *            each axis (rows first). The weights from the edge inwards:
+ *            0.00102838, 0.00759876, 0.03600077, 0.10936069, 0.21300554, 0.26601172
+ *   fields   ux = G x, uy = G y, uxx = G(x x), uyy = G(y y), uxy = G(x y);  cov = 121 / 120
+ *            vx = cov (uxx - ux ux), vy = cov (uyy - uy uy), vxy = cov (uxy - ux uy)
+ *   score    C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *            S = ((2 ux uy + C1) (2 vxy + C2)) / ((ux^2 + uy^2 + C1) (vx + vy + C2))
+ *   value    the mean of S over the (H - 10)(W - 10) VALID pixels -- at least 5 away from every border, so only windows that
+ *            lie wholly inside the image count -- accumulated in fp64; then the plain mean over the channels
+ *   borders  only the map sees them: G there reads the image through scipy's mode='reflect' (d c b a | a b c d | d c b a)
+ * The fields are taken of x - mx and y - my, mx and my the pixel in the middle of the workgroup's tile (0 when it is not finite),
+ * and the shift is added back to ux and uy: vx, vy and vxy do not change under a shift, but on a nearly flat image the
+ * cancellation in uxx - ux ux then leaves the differences of neighbouring pixels and not the rounding of their squares.
+ * All arithmetic is fp32, one rounding per operator, except the window's taps, which are fused multiply-adds, summed from the
+ * outer pair inwards: w5 (v[-5] + v[5]), then fma(w4, v[-4] + v[4], .), ..., the centre last. With x == y every S is exactly 1
+ * and so is the value. A NaN pixel makes the value NaN and the map NaN in its 11 x 11 neighbourhood; nothing is clamped.
+ *
+ * Backward: with L = grad * value, per valid pixel q (zero elsewhere), A1, A2 the numerator's factors and B1, B2 the
+ * denominator's, P = A1 / B1, Q = A2 / B2:
+ *   dS/dux  = 2 (uy Q - ux S) / B1 + 2 cov (ux S - uy P) / B2       dS/duxx = -cov S / B2       dS/duxy = 2 cov P / B2
+ *   grad_x  = (grad / (channels (H - 10)(W - 10))) * (Gt[dS/dux] + 2 x Gt[dS/duxx] + y Gt[dS/duxy])
+ * Gt is the transpose of the valid filter: the same window over the three fields with zeros outside the valid region. At
+ * x == y the three terms cancel to the bit: grad_x is exactly zero. The fields are recomputed, nothing is kept from a forward.
+ *
+ * One workgroup per (tile of SHACIRA_SSIM_TILE_H x SHACIRA_SSIM_TILE_W pixels, channel), tiles counted from pixel (0, 0).
+ * Reduction order: a tile's valid scores are added in fp64 by lane shuffles and then over its four waves; a one-workgroup
+ * finishing kernel adds the partials of a channel (thread t the tiles t, t + 1024, ..., then a binary tree over the threads),
+ * divides by the valid pixels and averages the channels. No floating-point atomics: two calls on the same operands return the
+ * same bits in value, map and grad_x.
+ *
+ *   workspace  shacira_ssim_workspace_bytes(H, W, channels, backward) bytes, 16-byte aligned. Forward (backward == 0): one
+ *              fp64 partial per (channel, tile). Backward: the three derivative planes, 3 * channels * H * W fp32. 0 when
+ *              the arguments are invalid. The call initialises what it reads.
+ * Bounds: H, W >= SHACIRA_SSIM_WINDOW (skimage raises below it), 1 <= channels <= pixel_stride <= 65535, at most 2^31 - 1
+ * tiles; all index arithmetic is 64-bit (a gigapixel image is in range). Validation happens before any HIP call: a bad size,
+ * channel count or data_range and NULL x, y, value, grad or grad_x return SHACIRA_EINVAL and nothing is enqueued; a workspace
+ * below the query returns SHACIRA_EWORKSPACE. Everything runs on `stream`: no synchronisation, no allocation, capturable.
+ */
+#define SHACIRA_SSIM_WINDOW 11
+#define SHACIRA_SSIM_TILE_H 16
+#define SHACIRA_SSIM_TILE_W 64
+SHACIRA_API size_t shacira_ssim_workspace_bytes(int64_t height, int64_t width, int channels, int backward);
+SHACIRA_API int shacira_ssim_forward(int64_t height, int64_t width, int pixel_stride, int channels, const float *x,
+                                     const float *y, float data_range, double *value, float *map, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+SHACIRA_API int shacira_ssim_backward(int64_t height, int64_t width, int pixel_stride, int channels, const float *x,
+                                      const float *y, float data_range, const float *grad, float *grad_x, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

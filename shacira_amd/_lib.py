@@ -21,6 +21,7 @@ MESH_SDF_PASS_TRIANGLES, MESH_SDF_CHUNK_GRANULE = 16384, 32   # SHACIRA_MESH_SDF
 MESH_CLOSEST_SIGNED = 1
 MESH_VOXELIZE_PASS_TRIANGLES = 32768                          # SHACIRA_MESH_VOXELIZE_PASS_TRIANGLES
 OCTREE_MAX_LEVEL = 10                                         # SHACIRA_OCTREE_MAX_LEVEL
+SSIM_WINDOW, SSIM_TILE_H, SSIM_TILE_W = 11, 16, 64            # SHACIRA_SSIM_* of the header
 
 _lock = threading.Lock()
 _lib = None
@@ -65,6 +66,9 @@ SIGNATURES = {
     "shacira_mesh_closest": (_i, [_i64, _i64, _p, _p, ctypes.c_int32, _p, _p, _p, _p, _sz, _p]),
     "shacira_mesh_voxelize_workspace_bytes": (_sz, [_i64, _i]),
     "shacira_mesh_voxelize": (_i, [_i64, _p, _i, _f, _p, _p, _p, _sz, _p]),
+    "shacira_ssim_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "shacira_ssim_forward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),
+    "shacira_ssim_backward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),
     "shacira_find_depth_bound": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),

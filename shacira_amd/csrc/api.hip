@@ -564,6 +564,41 @@ int shacira_mesh_voxelize(int64_t num_triangles, const float *triangles, int lev
                                        (hipStream_t)stream);
 }
 
+// ---- structural similarity -------------------------------------------------------------------------------------------------
+static bool ssim_args_ok(int64_t height, int64_t width, int pixel_stride, int channels) {
+    if (height < SHACIRA_SSIM_WINDOW || width < SHACIRA_SSIM_WINDOW || channels < 1 || channels > pixel_stride) return false;
+    if (pixel_stride > 65535) return false;                                  // the channel is a grid dimension
+    if (height > INT64_MAX / width / pixel_stride / 16) return false;         // byte offsets and the planes stay inside int64
+    return ssim_tiles(height, width) <= INT32_MAX;
+}
+
+size_t shacira_ssim_workspace_bytes(int64_t height, int64_t width, int channels, int backward) {
+    if (!ssim_args_ok(height, width, channels, channels)) return 0;
+    return ssim_workspace(height, width, channels, backward != 0);
+}
+
+int shacira_ssim_forward(int64_t height, int64_t width, int pixel_stride, int channels, const float *x, const float *y,
+                         float data_range, double *value, float *map, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+    if (!ssim_args_ok(height, width, pixel_stride, channels) || !(data_range > 0.f) || std::isinf(data_range))
+        return SHACIRA_EINVAL;
+    if (!x || !y || !value) return SHACIRA_EINVAL;
+    if (!workspace || workspace_bytes < ssim_workspace(height, width, channels, false)) return SHACIRA_EWORKSPACE;
+    return (int)ssim_forward_dispatch(height, width, pixel_stride, channels, x, y, data_range, value, map, workspace,
+                                      (hipStream_t)stream);
+}
+
+int shacira_ssim_backward(int64_t height, int64_t width, int pixel_stride, int channels, const float *x, const float *y,
+                          float data_range, const float *grad, float *grad_x, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    if (!ssim_args_ok(height, width, pixel_stride, channels) || !(data_range > 0.f) || std::isinf(data_range))
+        return SHACIRA_EINVAL;
+    if (!x || !y || !grad || !grad_x) return SHACIRA_EINVAL;
+    if (!workspace || workspace_bytes < ssim_workspace(height, width, channels, true)) return SHACIRA_EWORKSPACE;
+    return (int)ssim_backward_dispatch(height, width, pixel_stride, channels, x, y, data_range, grad, grad_x, workspace,
+                                       (hipStream_t)stream);
+}
+
 // ---- sphere tracing over ray packs ---------------------------------------------------------------------------------------
 static bool trace_counts_ok(int64_t num_packs, int64_t num_nugs) {
     return num_packs >= 0 && num_nugs >= 0 && num_packs <= INT32_MAX && num_nugs <= INT32_MAX && num_packs <= num_nugs;

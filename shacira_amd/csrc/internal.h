@@ -152,6 +152,15 @@ size_t mesh_voxelize_workspace(int64_t t);
 hipError_t mesh_voxelize_dispatch(int64_t t, const float *tris, int level, float margin, uint32_t *words, uint8_t *grid,
                                   void *workspace, hipStream_t s);
 
+// ssim.hip: structural similarity of two [H, W, cin] fp32 images over their first C channels (arguments checked by the entry
+// points). Forward: value[0] fp64, map [H, W, C] or NULL; backward: grad_x [H, W, cin] for the device scalar grad[0]
+int64_t ssim_tiles(int64_t H, int64_t W);
+size_t ssim_workspace(int64_t H, int64_t W, int C, bool backward);
+hipError_t ssim_forward_dispatch(int64_t H, int64_t W, int cin, int C, const float *x, const float *y, float data_range,
+                                 double *value, float *map, void *workspace, hipStream_t s);
+hipError_t ssim_backward_dispatch(int64_t H, int64_t W, int cin, int C, const float *x, const float *y, float data_range,
+                                  const float *grad, float *grad_x, void *workspace, hipStream_t s);
+
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
                                    const float *depth, int32_t *out, hipStream_t s);

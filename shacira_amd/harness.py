@@ -207,6 +207,13 @@ class ImageFitter:
         return rgb_loss, psnr, float(avg_bits)
 
 
+def evaluate_image(pred, gt):
+    """{"psnr", "ssim"} of one [H, W, 3] image against its ground truth: the two numbers ``MultiviewTrainer.evaluate_metrics``
+    accumulates per validation image (wisp/trainers/multiview_trainer.py:194-198). Images in [0, 1], on the host or the device."""
+    from .wisp.ops.image.metrics import psnr, ssim
+    return {"psnr": psnr(pred[..., :3], gt[..., :3]), "ssim": ssim(pred[..., :3], gt[..., :3])}
+
+
 def _require_device_temperature(latent_dec, who):
     """The graph-captured fitters keep the SGA temperature in ONE device float that the decode kernel reads. Only the single
     fused SGA decode (`shacira_latent_decode_sga_*_tdev`) has such an entry point: the per-row MLP decoder, the hierarchical and

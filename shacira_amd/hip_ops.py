@@ -1034,3 +1034,63 @@ def mesh_voxelize(triangles, level, margin=0.5, with_grid=True):
                                      _stream(triangles))
     _lib.check(rc, "mesh_voxelize")
     return words, (grid.view(torch.bool) if with_grid else None)
+
+
+# ---- structural similarity (include/shacira_hip.h, shacira_ssim_forward / shacira_ssim_backward) -------------------------------
+def _ssim_operands(pred, target, channels):
+    """The checked operands of the two SSIM calls: (pred, target, H, W, Cin, C) with both images contiguous fp32 [H, W, Cin] on
+    the device of ``pred``. Sizes below the 11-pixel window raise ValueError, as skimage does."""
+    _need_gpu(pred, target)
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise RuntimeError(f"shacira_amd: ssim expects two [H, W, C] images of one shape, got {tuple(pred.shape)} and "
+                           f"{tuple(target.shape)}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise RuntimeError("shacira_amd: ssim expects fp32 images")
+    H, W, Cin = pred.shape
+    C = Cin if channels is None else int(channels)
+    if H < _lib.SSIM_WINDOW or W < _lib.SSIM_WINDOW:
+        raise ValueError(f"win_size exceeds image extent: the {_lib.SSIM_WINDOW}-pixel window does not fit a {H} x {W} image")
+    if not 1 <= C <= Cin:
+        raise RuntimeError(f"shacira_amd: ssim over {C} channels of a {Cin}-channel image")
+    return pred.detach().contiguous(), target.detach().to(pred.device).contiguous(), H, W, Cin, C
+
+
+def ssim_forward(pred, target, channels=None, data_range=1.0, with_map=False):
+    """(value, map): the SSIM of ``pred`` against ``target`` ([H, W, Cin] fp32 on the device) over their first ``channels``
+    channels (all by default) as ONE fp64 on the device, and the per-pixel map fp32 [H, W, channels] (``None`` unless
+    ``with_map``). No host read-back: capturable. Deterministic to the bit."""
+    pred, target, H, W, Cin, C = _ssim_operands(pred, target, channels)
+    dev = pred.device
+    value = torch.empty((), dtype=torch.float64, device=dev)
+    smap = torch.empty((H, W, C), dtype=torch.float32, device=dev) if with_map else None
+    L = _lib.lib()
+    with _on_device(dev):
+        nbytes = int(L.shacira_ssim_workspace_bytes(H, W, C, 0))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_ssim_forward(H, W, Cin, C, _ptr(pred), _ptr(target), float(data_range), _ptr(value), _ptr(smap),
+                                    _ptr(ws), nbytes, _stream(pred))
+    _lib.check(rc, "ssim_forward")
+    return value, smap
+
+
+def ssim_backward(pred, target, grad, channels=None, data_range=1.0):
+    """d(grad * SSIM)/d(pred): fp32 [H, W, Cin], exactly zero in the channels beyond ``channels``. ``grad`` is a one-element
+    tensor on the device (any float dtype) or a number. There is no gradient with respect to ``target``."""
+    pred, target, H, W, Cin, C = _ssim_operands(pred, target, channels)
+    dev = pred.device
+    if torch.is_tensor(grad):
+        _need_gpu(grad)
+        if grad.numel() != 1:
+            raise RuntimeError(f"shacira_amd: ssim_backward expects a scalar grad, got {tuple(grad.shape)}")
+        grad = grad.detach().to(dtype=torch.float32).reshape(1).contiguous()
+    else:
+        grad = torch.full((1,), float(grad), dtype=torch.float32, device=dev)
+    grad_pred = torch.empty((H, W, Cin), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with _on_device(dev):
+        nbytes = int(L.shacira_ssim_workspace_bytes(H, W, C, 1))
+        ws = _workspace(dev, nbytes)
+        rc = L.shacira_ssim_backward(H, W, Cin, C, _ptr(pred), _ptr(target), float(data_range), _ptr(grad), _ptr(grad_pred),
+                                     _ptr(ws), nbytes, _stream(pred))
+    _lib.check(rc, "ssim_backward")
+    return grad_pred
