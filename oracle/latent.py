@@ -66,7 +66,7 @@ def sga_quantise(latent, uniforms, temperature, diff_sampling=True):
     through the sampler) and a straight-through floor (dq/dw = s0 + s1)."""
     w = latent.astype(np.float64)
     T = float(temperature)
-    lim = 1.0 - 1e-6
+    lim = float(f32(1.0 - 1e-6))    # torch.clamp on a float32 tensor rounds the bound to float32
     wf = np.floor(w)
     wc = wf + 1.0
     df = np.clip(w - wf, -lim, lim)
@@ -81,8 +81,8 @@ def sga_quantise(latent, uniforms, temperature, diff_sampling=True):
     s0, s1 = np.exp(z0 - lse), np.exp(z1 - lse)
     q = wf * s0 + wc * s1
     if diff_sampling:
-        in_f = (w - wf > -lim) & (w - wf < lim)
-        in_c = (wc - w > -lim) & (wc - w < lim)
+        in_f = (w - wf >= -lim) & (w - wf <= lim)    # torch.clamp hands the gradient on at the bounds themselves
+        in_c = (wc - w >= -lim) & (wc - w <= lim)
         dz = ((1.0 - np.tanh(dc) ** 2) * in_c + (1.0 - np.tanh(df) ** 2) * in_f) / (T * T)   # d(z1 - z0)/dw
         dq = (wc - wf) * s0 * s1 * dz
     else:
@@ -124,7 +124,8 @@ def _softplus(h):
 
 
 def _sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    with np.errstate(over="ignore"):       # exp(-x) = inf -> 0, the limit
+        return 1.0 / (1.0 + np.exp(-x))
 
 
 def cdf(x, params, num_layers):
@@ -161,19 +162,92 @@ def _cdf_backward(params, trace_and_x, s, g):
     return dx, dp
 
 
-def entropy_bits(latent, noise, params, num_layers):
-    """total bits (float64 scalar); noise None -> validation rule round(latent)."""
-    w = (latent.astype(f32) + noise.astype(f32)).astype(f32) if noise is not None else np.rint(latent.astype(f32))
-    sp, _ = cdf((w + f32(0.5)).astype(f32), params, num_layers)
-    sn, _ = cdf((w - f32(0.5)).astype(f32), params, num_layers)
+def _cdf_backward_abs(params, trace_and_x, du0):
+    """_cdf_backward with every term taken absolutely (|x|, |tanh u|, |tanh a|), started from du0 >= 0 [T,C], the weight of
+    each row at the sigmoid's argument: -> (sum-of-absolute-terms counterpart of dL/dx_in [T,C] and of dparams [4,3,C])."""
+    trace, xin4 = trace_and_x
+    dp = np.zeros(params.shape, np.float64)
+    sgh = lambda h: np.where(h > 20.0, 1.0, _sigmoid(h.astype(np.float64)))
+    du = du0
+    dp[3, 0] = (du * np.abs(xin4)).sum(0) * sgh(params[3, 0])
+    dp[3, 1] = du.sum(0)
+    dx = du * _softplus(params[3, 0])
+    for (k, xin, th) in reversed(trace):
+        ta = np.abs(np.tanh(params[k, 2].astype(np.float64)))
+        dp[k, 2] = (dx * np.abs(th)).sum(0) * (1.0 - ta * ta)
+        du = dx * (1.0 + (1.0 - th * th) * ta)
+        dp[k, 0] = (du * np.abs(xin)).sum(0) * sgh(params[k, 0])
+        dp[k, 1] = du.sum(0)
+        dx = du * _softplus(params[k, 0])
+    return dx, dp
+
+
+def _entropy_input(latent, noise):
+    """float32 like the reference: latent + noise (training) or round(latent) (validation)."""
+    return (latent.astype(f32) + noise.astype(f32)).astype(f32) if noise is not None else np.rint(latent.astype(f32))
+
+
+def entropy_elements(latent, noise, params, num_layers):
+    """Per-element pieces of the bit estimate in float64 (the input w is the reference's float32 sum or round):
+    dict(bits [T,C] (clamped to [0, 50]), prob, s_hi, s_lo (the CDF at w + 0.5 and w - 0.5), ds_hi, ds_lo (their derivatives
+    with respect to w), slope_hi, slope_lo (d(sigmoid argument)/dw with every factor taken absolutely, the scale of a rounding
+    bound on ds), trace_hi, trace_lo (for _cdf_backward / _cdf_backward_abs))."""
+    w = _entropy_input(latent, noise)
+    sp, tp = cdf((w + f32(0.5)).astype(f32), params, num_layers)
+    sn, tn = cdf((w - f32(0.5)).astype(f32), params, num_layers)
     prob = sp - sn
     bits = np.clip(-np.log(prob + 1e-10) / np.log(2.0), 0, 50)
-    return float(bits.sum())
+    one = np.ones_like(sp)
+    return dict(bits=bits, prob=prob, s_hi=sp, s_lo=sn, ds_hi=_cdf_backward(params, tp, sp, one)[0],
+                ds_lo=_cdf_backward(params, tn, sn, one)[0], slope_hi=_cdf_backward_abs(params, tp, one)[0],
+                slope_lo=_cdf_backward_abs(params, tn, one)[0], trace_hi=tp, trace_lo=tn)
+
+
+def entropy_bits_elements(latent, noise, params, num_layers):
+    """float64 bits of every element [T, C]; noise None -> validation rule round(latent)."""
+    return entropy_elements(latent, noise, params, num_layers)["bits"]
+
+
+def entropy_bits(latent, noise, params, num_layers):
+    """total bits (float64 scalar); noise None -> validation rule round(latent)."""
+    return float(entropy_bits_elements(latent, noise, params, num_layers).sum())
+
+
+def entropy_elements_f32(latent, noise, params, num_layers):
+    """The same formulas as the fp32 reference evaluates them: np.float32 at every step, in the reference's order
+    (bit_estimator.py:38-44, latent_grid.py:132-135), libm tanh / exp / log. It states what fp32 gives where fp32 and fp64
+    legitimately part: in the upper tail both sigmoids round towards 1 and prob is 0 or a few ulps of 1; and where
+    prob + 1e-10 rounds to exactly 1 the bits are -0.0, which clamp(., 0, 50) passes WITH its gradient (``passes``), while in
+    float64 the bits are negative there and the clamp masks it.
+    -> dict(bits [T,C] float32 (clamped), prob, q = prob + 1e-10, s_hi, s_lo, passes (bool: the clamp hands the gradient on))."""
+    prm = params.astype(f32)
+
+    def softplus(h):
+        with np.errstate(over="ignore"):
+            return np.where(h > f32(20.0), h, np.log1p(np.exp(np.minimum(h, f32(20.0)), dtype=f32), dtype=f32)).astype(f32)
+
+    def cdf32(x):
+        for k in range(3):
+            if num_layers > k + 1:
+                u = ((x * softplus(prm[k, 0])).astype(f32) + prm[k, 1]).astype(f32)
+                x = (u + (np.tanh(u, dtype=f32) * np.tanh(prm[k, 2], dtype=f32)).astype(f32)).astype(f32)
+        z = ((x * softplus(prm[3, 0])).astype(f32) + prm[3, 1]).astype(f32)
+        with np.errstate(over="ignore"):
+            return (f32(1.0) / (f32(1.0) + np.exp(-z, dtype=f32)).astype(f32)).astype(f32)
+
+    w = _entropy_input(latent, noise)
+    s_hi, s_lo = cdf32((w + f32(0.5)).astype(f32)), cdf32((w - f32(0.5)).astype(f32))
+    prob = (s_hi - s_lo).astype(f32)
+    q = (prob + f32(1e-10)).astype(f32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        raw = ((f32(-1.0) * np.log(q, dtype=f32)).astype(f32) / f32(np.log(2.0))).astype(f32)
+    passes = (raw >= 0) & (raw <= 50)                   # -0.0 >= 0: q == 1 passes
+    return dict(bits=np.clip(raw, f32(0), f32(50)).astype(f32), prob=prob, q=q, s_hi=s_hi, s_lo=s_lo, passes=passes)
 
 
 def entropy_bits_backward(latent, noise, params, num_layers, grad_total=1.0):
     """-> (grad_latent [T,C] (zeros in validation mode), grad_params [4,3,C])."""
-    w = (latent.astype(f32) + noise.astype(f32)).astype(f32) if noise is not None else np.rint(latent.astype(f32))
+    w = _entropy_input(latent, noise)
     sp, tp = cdf((w + f32(0.5)).astype(f32), params, num_layers)
     sn, tn = cdf((w - f32(0.5)).astype(f32), params, num_layers)
     q = sp - sn + 1e-10

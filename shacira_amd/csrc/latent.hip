@@ -128,12 +128,16 @@ __device__ __forceinline__ void sga_quantise(float w, float u0, float u1, float 
     const float s0 = expf(z0 - lse), s1 = expf(z1 - lse);
     q = wf * s0 + wc * s1;
     if (diff) {
-        const float in_f = (a > -lim && a < lim) ? 1.0f : 0.0f, in_c = (b > -lim && b < lim) ? 1.0f : 0.0f;
+        // torch.clamp hands the gradient on at the bounds themselves (w = -0.999999: b == lim)
+        const float in_f = (a >= -lim && a <= lim) ? 1.0f : 0.0f, in_c = (b >= -lim && b <= lim) ? 1.0f : 0.0f;
         dq = s0 * s1 * ((1.0f - tc * tc) * in_c + (1.0f - tf_ * tf_) * in_f) / (T * T);
     } else {
         dq = s0 + s1;
     }
 }
+
+// torch.clamp(v, -c, c): a NaN stays a NaN (fminf / fmaxf would return the bound)
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return v < -c ? -c : (v > c ? c : v); }
 
 template <int LD, int F, bool SGA>
 __device__ __forceinline__ void decode_row(const DecodeConsts<LD, F> &p, const float *__restrict__ latent, int64_t r,
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void latent_decode_fwd_kernel(
 #pragma unroll
         for (int j = 0; j < F; ++j) {
             float v = y[j];
-            if (clampw > 0.0f) v = fminf(fmaxf(v, -clampw), clampw);
+            if (clampw > 0.0f) v = clamp_keep_nan(v, clampw);
             decoded[r * F + j] = v;
         }
     }
@@ -276,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void latent_decode_levels_fwd_kernel(
 #pragma unroll
         for (int j = 0; j < F; ++j) {
             float v = y[j];
-            if (clampw > 0.0f) v = fminf(fmaxf(v, -clampw), clampw);
+            if (clampw > 0.0f) v = clamp_keep_nan(v, clampw);
             decoded[r * F + j] = v;
         }
     }
@@ -506,7 +510,7 @@ __global__ __launch_bounds__(kThreads) void multi_decode_kernel(MultiArgs a) {
 #pragma unroll
             for (int j = 0; j < F; ++j) {
                 float v = y[j];
-                if (a.clampw > 0.0f) v = fminf(fmaxf(v, -a.clampw), a.clampw);
+                if (a.clampw > 0.0f) v = clamp_keep_nan(v, a.clampw);
                 a.decoded[r * F + j] = v;
             }
         } else {
@@ -693,11 +697,16 @@ template <int LD> struct CdfConsts {
 __device__ __forceinline__ float sigmoidf_ref(float x) { return __frcp_rn(1.0f + expf(-x)); }
 
 // tanh(u) = 1 - 2 / (exp(2u) + 1): one exp + one reciprocal instead of libm's ~120-instruction tanhf (the entropy backward was
-// VALU-bound at 1 300 instructions per table row and 246 VGPRs). Absolute error ~1e-7; it enters the CDF through
-// x = u + tanh(u) * tanh(a) and a sigmoid of slope <= 1/4, i.e. below the fp32 rounding of the CDF value itself.
+// VALU-bound at 1 300 instructions per table row and 246 VGPRs). Its error is ABSOLUTE, ~1e-7, so below |u| = 1/4, where the
+// difference cancels, the odd Taylor polynomial through u^9 takes over (truncation 8.9e-3 u^10 <= 8.5e-9 relative there):
+// tanh(u) enters x = u + tanh(u) * tanh(a), and every later layer multiplies x by its softplus(h) -- with h = 20 three layers
+// carry an absolute 1e-7 at u ~ 1e-4 to 2e-4 of the sigmoid's argument, 50 times the fp32 rounding of the CDF value.
 __device__ __forceinline__ float tanhf_fast(float u) {
     const float e = __expf(2.0f * u);               // (hardware exp2: its error reaches tanh scaled by <= 1/2) inf -> 1, 0 -> -1
-    return 1.0f - 2.0f * __frcp_rn(e + 1.0f);
+    const float big = 1.0f - 2.0f * __frcp_rn(e + 1.0f);
+    const float v = u * u;
+    const float p = fmaf(v, fmaf(v, fmaf(v, fmaf(v, 62.0f / 2835.0f, -17.0f / 315.0f), 2.0f / 15.0f), -1.0f / 3.0f), 1.0f);
+    return fabsf(u) < 0.25f ? u * p : big;          // a NaN takes the exp branch and stays a NaN
 }
 
 // CDF with the chain's intermediates kept for the backward (NL = num_layers; layers used: first NL-1 of f1..f3, then f4)
