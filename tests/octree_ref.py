@@ -51,30 +51,45 @@ def locate(coords, level, index_dtype=np.float32):
     return inside, cell, t
 
 
+class SortedCells:
+    """``level_points`` of one level with its keys sorted once: pass it wherever a ``level_points[l]`` goes when the same
+    index serves many calls (``cell_rank`` sorts a plain array on every call)."""
+
+    def __init__(self, level_points, level):
+        G = 1 << level
+        pts = np.asarray(level_points).astype(np.int64)
+        keys = (pts[:, 0] * G + pts[:, 1]) * G + pts[:, 2]
+        self.level = level
+        self.order = np.argsort(keys, kind="stable")
+        self.keys = keys[self.order]
+
+
 def cell_rank(level_points, level, cell, inside):
-    """Row of ``level_points`` that equals each cell, -1 where there is none (unoccupied) or the sample is not inside."""
+    """Row of ``level_points`` (an array or a ``SortedCells``) that equals each cell, -1 where there is none (unoccupied) or
+    the sample is not inside."""
     G = 1 << level
-    pts = np.asarray(level_points).astype(np.int64)
     rank = np.full(cell.shape[0], -1, dtype=np.int64)
-    if pts.shape[0] == 0:
+    sc = level_points if isinstance(level_points, SortedCells) else SortedCells(level_points, level)
+    assert sc.level == level
+    if sc.keys.shape[0] == 0:
         return rank
-    keys = (pts[:, 0] * G + pts[:, 1]) * G + pts[:, 2]
-    order = np.argsort(keys, kind="stable")
-    skeys = keys[order]
     ck = (cell[:, 0] * G + cell[:, 1]) * G + cell[:, 2]
-    pos = np.clip(np.searchsorted(skeys, ck), 0, skeys.shape[0] - 1)
-    found = inside & (skeys[pos] == ck)
-    rank[found] = order[pos[found]]
+    pos = np.clip(np.searchsorted(sc.keys, ck), 0, sc.keys.shape[0] - 1)
+    found = inside & (sc.keys[pos] == ck)
+    rank[found] = sc.order[pos[found]]
     return rank
 
 
-def weights(t):
-    """fp64 [N, 8]: w_k."""
-    w = np.ones((t.shape[0], 8), dtype=np.float64)
+def weights(t, weight_dtype=np.float64):
+    """fp64 [N, 8]: w_k. ``weight_dtype=np.float32`` rounds 1 - t and the product (x, then y, then z) to fp32: the weights
+    of a kernel that evaluates the contract's product in fp32, exactly (``t`` is an fp32 value already)."""
+    dt = weight_dtype
+    t = np.asarray(t).astype(dt)
+    w = np.ones((t.shape[0], 8), dtype=dt)
     for k in range(8):
         for a in range(3):
-            w[:, k] *= t[:, a] if CORNERS[k, a] else 1.0 - t[:, a]
-    return w
+            w[:, k] *= t[:, a] if CORNERS[k, a] else dt(1) - t[:, a]
+    return w.astype(np.float64)
 
 
 def _dweights(t):
@@ -127,8 +142,10 @@ def hit_any(coords, levels, level_points, index_dtype=np.float32):
     return any_hit
 
 
-def backward(coords, levels, level_points, trinkets, tables, grad_out, multiscale_sum, index_dtype=np.float32):
-    """-> (table gradients, one fp64 [C + 1, F] per level; coordinate gradient fp64 [N, 3]; its absolute-sum scale [N, 3])."""
+def backward(coords, levels, level_points, trinkets, tables, grad_out, multiscale_sum, index_dtype=np.float32,
+             weight_dtype=np.float64):
+    """-> (table gradients, one fp64 [C + 1, F] per level; coordinate gradient fp64 [N, 3]; its absolute-sum scale [N, 3]).
+    ``weight_dtype``: the precision of the table gradient's weights (``weights``); the sums are fp64 either way."""
     N = coords.shape[0]
     grad_out = np.asarray(grad_out, dtype=np.float64)
     grad_tables = []
@@ -145,7 +162,7 @@ def backward(coords, levels, level_points, trinkets, tables, grad_out, multiscal
         gt = np.zeros_like(table)
         if hit.any():
             rows = np.asarray(trinkets[l]).astype(np.int64)[rank[hit]]
-            w = weights(t[hit])
+            w = weights(t[hit], weight_dtype)
             contrib = w[..., None] * g[hit][:, None, :]                           # [n, 8, F]
             for j in range(F):
                 gt[:, j] = np.bincount(rows.reshape(-1), weights=contrib[..., j].reshape(-1), minlength=gt.shape[0])
@@ -156,3 +173,30 @@ def backward(coords, levels, level_points, trinkets, tables, grad_out, multiscal
             gscale[hit] += (G / 2) * (np.abs(dw) * adots[..., None]).sum(1)
         grad_tables.append(gt)
     return grad_tables, grad_coords, gscale
+
+
+def backward_scale(coords, levels, level_points, trinkets, table_rows, grad_out, multiscale_sum, index_dtype=np.float32,
+                   weight_dtype=np.float32):
+    """The scale of the table gradient's rounding error, next to ``backward``: per level (count int64 [C + 1], abs_sum
+    float64 [C + 1, F]). ``count`` = the corner contributions a row receives (eight per sample in an occupied cell,
+    zero-weight ones included); ``abs_sum`` A = sum |w_k * g| over them, with the weights of ``weights(t, weight_dtype)``.
+    ``table_rows[l]`` = C_l + 1."""
+    grad_out = np.abs(np.asarray(grad_out, dtype=np.float64))
+    out = []
+    for l, level in enumerate(levels):
+        rows_total = int(table_rows[l])
+        F = grad_out.shape[1] if multiscale_sum else grad_out.shape[1] // len(levels)
+        g = grad_out if multiscale_sum else grad_out[:, l * F:(l + 1) * F]
+        inside, cell, t = locate(coords, level, index_dtype)
+        rank = cell_rank(level_points[l], level, cell, inside)
+        hit = rank >= 0
+        count = np.zeros(rows_total, dtype=np.int64)
+        asum = np.zeros((rows_total, F))
+        if hit.any():
+            rows = np.asarray(trinkets[l]).astype(np.int64)[rank[hit]]
+            contrib = np.abs(weights(t[hit], weight_dtype))[..., None] * g[hit][:, None, :]
+            count = np.bincount(rows.reshape(-1), minlength=rows_total)
+            for j in range(F):
+                asum[:, j] = np.bincount(rows.reshape(-1), weights=contrib[..., j].reshape(-1), minlength=rows_total)
+        out.append((count, asum))
+    return out
