@@ -885,6 +885,89 @@ SHACIRA_API int shacira_rc_decode(const uint8_t *in_host, size_t len, const uint
                       int32_t *symbols_host);
 
 /*
+ * Interleaved rANS ("rans64"): the entropy codec that also runs on the device. 64 coder states advance in lockstep and
+ * share one stream of 16-bit words, so a 64-lane wavefront codes one block. Integer-exact: the host coder and the kernels
+ * produce the same bytes. Added within ABI 11 (new symbols only).
+ *
+ * Format of ONE channel. Inputs: T symbols s[i] in [0, nbins), nbins >= 2; the model freq[nbins] with sum 65536 and
+ * 1 <= freq <= 65535 for every symbol present (shacira_amd/codec.py, normalise_frequencies); cdf[k] = sum(freq[:k]);
+ * K = steps per block. A block is 64*K consecutive symbols, nblocks = ceil(T / (64*K)). The state is a 32-bit x in
+ * [2^16, 2^32), renormalised in 16-bit words. Lane l at step k of block b owns symbol i = b*64*K + k*64 + l and is active
+ * iff i < T; inactive lanes do nothing.
+ *
+ *   encode block b:  x[0..63] = 0x10000 ; words = []
+ *     for k = K-1 down to 0:
+ *       for each active lane l (s = its symbol, f = freq[s], c = cdf[s]):  emit[l] = x[l] >= (f << 16)
+ *       for lanes with emit, in INCREASING lane order:                     words.append(x[l] & 0xFFFF) ; x[l] >>= 16
+ *       for each active lane:                                              x[l] = ((x[l] / f) << 16) + (x[l] % f) + c
+ *     output: the 64 final states (u32, lane order) and words (u16), n_b = len(words)
+ *
+ *   decode block b:  x = states ; p = n_b
+ *     for k = 0 .. K-1:
+ *       for each active lane:  slot = x & 0xFFFF ; s = the k with cdf[k] <= slot < cdf[k+1]
+ *                              x = freq[s] * (x >> 16) + slot - cdf[s]
+ *       need[l] = active and x[l] < 0x10000 ; n = count(need) ; r[l] = rank of l among the needing lanes
+ *       x[l] = (x[l] << 16) | words[p - n + r[l]]  for needing lanes ; p -= n
+ *     on valid input p == 0 and every x == 0x10000 at the end
+ *
+ * Channel payload, little endian: n_b as u32 x nblocks | final states as u32 x 64 x nblocks, block-major | the words of
+ * block 0, block 1, ... as u16. The flush (count + states) is 260 bytes per block: 0.008 bit per symbol at K = 4096.
+ * A channel with nbins == 1 carries no payload (its freq would be 65536 and f << 16 would overflow); the decoder fills
+ * it with `lo`.
+ *
+ * Container (shacira_amd/codec.py writes and parses it): magic "SHCR\x02\x00" | u32 header length | JSON header
+ * {"coder":"rans64","rows":T,"latent_dim":ld,"steps":K,"channels":[{"lo","nbins","words"}...]} | zero padding to a
+ * multiple of 4 | per channel: the frequency table as u16 x nbins (65536 stored as 0), then the channel payload, each
+ * zero-padded to a multiple of 4.
+ *
+ * Host coder (HOST buffers, calling thread), 1 <= steps <= 65536:
+ *   shacira_rans_encode_bound  bytes that always hold the payload of n symbols (260 per block + 2 per symbol); 0 for bad steps
+ *   shacira_rans_encode        symbols -> channel payload; *out_len = bytes produced; SHACIRA_EWORKSPACE if `capacity` is
+ *                              below that. SHACIRA_EINVAL: model sum != 65536, a freq of 65536 (single-symbol channel),
+ *                              a symbol outside the model or with freq 0, bad steps, NULL.
+ *   shacira_rans_decode        exact inverse. Never reads outside in_host[0, len) or writes outside symbols_host[0, n),
+ *                              whatever the bytes: SHACIRA_EINVAL when len != 260*nblocks + 2*sum(n_b), a state is below
+ *                              2^16, a block needs more words than it holds (p < 0), or p != 0 / x != 0x10000 at the end.
+ *
+ * Device coder (one wavefront per (block, channel); everything on `stream`, no synchronisation, no allocation). lo_host,
+ * nbins_host, payload_offset_host, words_host are HOST arrays of latent_dim entries, copied into the kernel arguments;
+ * `cdf` is a device uint32 [latent_dim][cdf_stride] with cdf[c][0..nbins[c]]; channels with nbins < 2 are skipped.
+ * nblocks = ceil(num_rows / (64*steps)); latent_dim <= 16, else SHACIRA_EDTYPE. All validation precedes any HIP call;
+ * num_rows == 0 returns 0 and launches nothing.
+ *   shacira_latent_rans_encode  reads the fp32 [num_rows, latent_dim] latents, codes symbol (int)rint(v) - lo[c] (clamped
+ *                               into the model). Writes counts u32 [ld][nblocks], states u32 [ld][nblocks][64] and each
+ *                               block's words into its bound-sized slot, slots u16 [ld][nblocks][64*steps].
+ *   shacira_latent_rans_pack    moves counts, states and words to their place in the channel payloads: `out` + the
+ *                               channel's payload_offset (bytes, multiple of 4); block_start device int64 [ld][nblocks] =
+ *                               exclusive prefix of the channel's counts; words_host[c] = their sum. SHACIRA_EINVAL when a
+ *                               payload would end beyond out_bytes. Starts and counts are clamped into the channel's words.
+ *   shacira_latent_rans_decode  `container` = the container's bytes on the device (4-byte aligned); writes
+ *                               symbol + lo[c] as fp32 into out [num_rows, latent_dim]. cdf is searched from LDS when
+ *                               max nbins < 4096, from global memory otherwise. Every word index is clamped into its
+ *                               block's [0, n_b), the block into the channel's words, the symbol into [0, nbins): corrupt
+ *                               bytes give wrong values, never an access outside the container. *error (device int32,
+ *                               zeroed by the caller) is set to 1 on an underflow, a state below 2^16 or a bad end state.
+ *                               SHACIRA_EINVAL when a payload would end beyond container_bytes.
+ */
+SHACIRA_API size_t shacira_rans_encode_bound(int64_t num_symbols_to_code, int steps);
+SHACIRA_API int shacira_rans_encode(const int32_t *symbols_host, int64_t n, const uint32_t *freq_host, int num_symbols,
+                        int steps, uint8_t *out_host, size_t capacity, size_t *out_len);
+SHACIRA_API int shacira_rans_decode(const uint8_t *in_host, size_t len, const uint32_t *freq_host, int num_symbols,
+                        int64_t n, int steps, int32_t *symbols_host);
+SHACIRA_API int shacira_latent_rans_encode(int64_t num_rows, int latent_dim, const float *latent, const int32_t *lo_host,
+                               const int32_t *nbins_host, const uint32_t *cdf, int cdf_stride, int steps,
+                               uint32_t *counts, uint32_t *states, uint16_t *slots, void *stream);
+SHACIRA_API int shacira_latent_rans_pack(int64_t num_rows, int latent_dim, const int32_t *nbins_host, int steps,
+                             const uint32_t *counts, const uint32_t *states, const uint16_t *slots,
+                             const int64_t *block_start, const int64_t *payload_offset_host, const int64_t *words_host,
+                             uint8_t *out, size_t out_bytes, void *stream);
+SHACIRA_API int shacira_latent_rans_decode(int64_t num_rows, int latent_dim, const uint8_t *container,
+                               size_t container_bytes, const int32_t *lo_host, const int32_t *nbins_host,
+                               const int64_t *payload_offset_host, const int64_t *words_host, const uint32_t *cdf,
+                               int cdf_stride, const int64_t *block_start, int steps, float *out, int32_t *error,
+                               void *stream);
+
+/*
  * Volume integration over variable-length sample packs and sample generation on a dense occupancy grid -- the steps
  * either side of the hash-grid lookup in the NeRF pipeline. The reference runs them through kaolin 0.13 (un-vendored):
  * `spc_render.exponential_integration` / `sum_reduce` (call sites wisp/tracers/packed_rf_tracer.py:131-151),

@@ -100,6 +100,12 @@ SIGNATURES = {
     "shacira_rc_encode_bound": (_sz, [_i64]),
     "shacira_rc_encode": (_i, [_p, _i64, _p, _i, _p, _sz, _p]),
     "shacira_rc_decode": (_i, [_p, _sz, _p, _i, _i64, _p]),
+    "shacira_rans_encode_bound": (_sz, [_i64, _i]),
+    "shacira_rans_encode": (_i, [_p, _i64, _p, _i, _i, _p, _sz, _p]),
+    "shacira_rans_decode": (_i, [_p, _sz, _p, _i, _i64, _i, _p]),
+    "shacira_latent_rans_encode": (_i, [_i64, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "shacira_latent_rans_pack": (_i, [_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "shacira_latent_rans_decode": (_i, [_i64, _i, _p, _sz, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p]),
     "shacira_pack_integrate_forward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p]),
     "shacira_pack_integrate_backward": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "shacira_pack_sum": (_i, [_i64, _i64, _i, _p, _p, _p, _p]),

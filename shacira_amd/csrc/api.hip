@@ -953,6 +953,61 @@ int shacira_rc_decode(const uint8_t *in_host, size_t len, const uint32_t *freq_h
     return rc_decode(in_host, len, freq_host, num_symbols, n, symbols_host);
 }
 
+size_t shacira_rans_encode_bound(int64_t n, int steps) {
+    return rans_steps_ok(steps) ? rans_encode_bound(n < 0 ? 0 : n, steps) : 0;
+}
+
+int shacira_rans_encode(const int32_t *symbols_host, int64_t n, const uint32_t *freq_host, int num_symbols, int steps,
+                        uint8_t *out_host, size_t capacity, size_t *out_len) {
+    return rans_encode(symbols_host, n, freq_host, num_symbols, steps, out_host, capacity, out_len);
+}
+
+int shacira_rans_decode(const uint8_t *in_host, size_t len, const uint32_t *freq_host, int num_symbols, int64_t n,
+                        int steps, int32_t *symbols_host) {
+    return rans_decode(in_host, len, freq_host, num_symbols, n, steps, symbols_host);
+}
+
+int shacira_latent_rans_encode(int64_t num_rows, int latent_dim, const float *latent, const int32_t *lo_host,
+                               const int32_t *nbins_host, const uint32_t *cdf, int cdf_stride, int steps,
+                               uint32_t *counts, uint32_t *states, uint16_t *slots, void *stream) {
+    int rc = rans_device_args_ok(num_rows, latent_dim, nbins_host, cdf_stride, steps, nullptr, nullptr, 0);
+    if (rc) return rc;
+    if (!lo_host) return SHACIRA_EINVAL;
+    if (num_rows == 0) return 0;
+    if (!latent || !cdf || !counts || !states || !slots) return SHACIRA_EINVAL;
+    return (int)rans_encode_launch(latent, num_rows, latent_dim, lo_host, nbins_host, cdf, cdf_stride, steps, counts,
+                                   states, slots, (hipStream_t)stream);
+}
+
+int shacira_latent_rans_pack(int64_t num_rows, int latent_dim, const int32_t *nbins_host, int steps,
+                             const uint32_t *counts, const uint32_t *states, const uint16_t *slots,
+                             const int64_t *block_start, const int64_t *payload_offset_host, const int64_t *words_host,
+                             uint8_t *out, size_t out_bytes, void *stream) {
+    if (!payload_offset_host || !words_host) return SHACIRA_EINVAL;
+    int rc = rans_device_args_ok(num_rows, latent_dim, nbins_host, INT32_MAX, steps, payload_offset_host, words_host,
+                                 out_bytes);
+    if (rc) return rc;
+    if (num_rows == 0) return 0;
+    if (!counts || !states || !slots || !block_start || !out) return SHACIRA_EINVAL;
+    return (int)rans_pack_launch(num_rows, latent_dim, nbins_host, steps, counts, states, slots, block_start,
+                                 payload_offset_host, words_host, out, (hipStream_t)stream);
+}
+
+int shacira_latent_rans_decode(int64_t num_rows, int latent_dim, const uint8_t *container, size_t container_bytes,
+                               const int32_t *lo_host, const int32_t *nbins_host, const int64_t *payload_offset_host,
+                               const int64_t *words_host, const uint32_t *cdf, int cdf_stride,
+                               const int64_t *block_start, int steps, float *out, int32_t *error, void *stream) {
+    if (!payload_offset_host || !words_host) return SHACIRA_EINVAL;
+    int rc = rans_device_args_ok(num_rows, latent_dim, nbins_host, cdf_stride, steps, payload_offset_host, words_host,
+                                 container_bytes);
+    if (rc) return rc;
+    if (!lo_host || !error) return SHACIRA_EINVAL;
+    if (num_rows == 0) return 0;
+    if (!container || !cdf || !block_start || !out) return SHACIRA_EINVAL;
+    return (int)rans_decode_launch(container, num_rows, latent_dim, lo_host, nbins_host, payload_offset_host, words_host,
+                                   cdf, cdf_stride, block_start, steps, out, error, (hipStream_t)stream);
+}
+
 static int pack_args_ok(int64_t S, int64_t R, int C) {
     if (S < 0 || R < 0 || C < 1) return SHACIRA_EINVAL;
     if (C > 16) return SHACIRA_EDTYPE;

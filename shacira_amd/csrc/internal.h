@@ -233,6 +233,23 @@ hipError_t symbol_histogram_launch(const float *latent, int64_t rows, int ld, co
 size_t rc_encode_bound(int64_t n);
 int rc_encode(const int32_t *sym, int64_t n, const uint32_t *freq, int nsym, uint8_t *out, size_t cap, size_t *len);
 int rc_decode(const uint8_t *in, size_t len, const uint32_t *freq, int nsym, int64_t n, int32_t *sym);
+// interleaved rANS ("rans64"): host coder, and one wavefront per (block, channel) on the device
+bool rans_steps_ok(int steps);
+size_t rans_encode_bound(int64_t n, int steps);
+int rans_encode(const int32_t *sym, int64_t n, const uint32_t *freq, int nsym, int steps, uint8_t *out, size_t cap,
+                size_t *len);
+int rans_decode(const uint8_t *in, size_t len, const uint32_t *freq, int nsym, int64_t n, int steps, int32_t *sym);
+int rans_device_args_ok(int64_t rows, int ld, const int32_t *nbins, int cdf_stride, int steps, const int64_t *payload,
+                        const int64_t *words, size_t bytes);
+hipError_t rans_encode_launch(const float *latent, int64_t rows, int ld, const int32_t *lo, const int32_t *nbins,
+                              const uint32_t *cdf, int cdf_stride, int steps, uint32_t *counts, uint32_t *states,
+                              uint16_t *slots, hipStream_t s);
+hipError_t rans_pack_launch(int64_t rows, int ld, const int32_t *nbins, int steps, const uint32_t *counts,
+                            const uint32_t *states, const uint16_t *slots, const int64_t *block_start,
+                            const int64_t *payload, const int64_t *words, uint8_t *out, hipStream_t s);
+hipError_t rans_decode_launch(const uint8_t *data, int64_t rows, int ld, const int32_t *lo, const int32_t *nbins,
+                              const int64_t *payload, const int64_t *words, const uint32_t *cdf, int cdf_stride,
+                              const int64_t *block_start, int steps, float *out, int32_t *error, hipStream_t s);
 
 // render.hip
 hipError_t pack_integrate_launch(bool bwd, int64_t R, int C, const float *feats, const float *tau,

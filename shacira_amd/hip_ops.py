@@ -10,6 +10,7 @@ import functools
 import threading
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -783,6 +784,84 @@ def latent_symbol_counts(latent):
         _lib.check(L.shacira_latent_symbol_histogram(rows, ld, _ptr(latent), _ptr(minmax), nbins, _ptr(counts),
                                                      _stream(latent)), "shacira_latent_symbol_histogram")
     return mm[:, 0].long(), counts
+
+
+def _rans_host_arrays(lo, nbins, payload, words):
+    ld = len(nbins)
+    return ((ctypes.c_int32 * ld)(*[int(v) for v in lo]), (ctypes.c_int32 * ld)(*[int(v) for v in nbins]),
+            (ctypes.c_int64 * ld)(*[int(v) for v in payload]), (ctypes.c_int64 * ld)(*[int(v) for v in words]))
+
+
+def latent_rans_encode(latent, lo, nbins, cdf, steps):
+    """rans64 channel payloads of ``round(latent)`` (include/shacira_hip.h, "Interleaved rANS"), coded on the device.
+
+    ``latent`` fp32 [rows, ld] on the GPU; ``lo`` / ``nbins`` per channel (host); ``cdf`` uint32 numpy [ld, stride] with
+    ``cdf[c, :nbins[c] + 1]`` the channel's cumulative frequencies. Returns one ``bytes`` per channel (empty for
+    channels with fewer than two bins). The kernels read the fp32 table itself; one read-back of the per-block word
+    counts sizes the output, one copy brings the packed payloads to the host."""
+    _need_gpu(latent)
+    if latent.dtype != torch.float32 or latent.dim() != 2:
+        raise RuntimeError("latent_rans_encode: expected an fp32 [rows, latent_dim] tensor")
+    latent = latent.detach().contiguous()
+    rows, ld = latent.shape
+    if rows == 0:
+        return [b""] * ld
+    steps = int(steps)
+    nblocks = -(-rows // (64 * steps))
+    dev = latent.device
+    cdf = np.ascontiguousarray(cdf, dtype=np.uint32)
+    L = _lib.lib()
+    with _on_device(dev):
+        cdf_dev = torch.from_numpy(cdf.view(np.int32)).to(dev)
+        counts = torch.empty((ld, nblocks), dtype=torch.int32, device=dev)
+        states = torch.empty((ld, nblocks, 64), dtype=torch.int32, device=dev)
+        slots = torch.empty((ld, nblocks, 64 * steps), dtype=torch.int16, device=dev)
+        lo_h, nb_h, _, _ = _rans_host_arrays(lo, nbins, [0] * ld, [0] * ld)
+        _lib.check(L.shacira_latent_rans_encode(rows, ld, _ptr(latent), lo_h, nb_h, _ptr(cdf_dev), cdf.shape[1], steps,
+                                                _ptr(counts), _ptr(states), _ptr(slots), _stream(latent)),
+                   "shacira_latent_rans_encode")
+        n_b = counts.cpu().numpy().astype(np.int64)                  # the one read-back: sizes the output
+        words = n_b.sum(axis=1)
+        start = np.cumsum(n_b, axis=1) - n_b
+        sizes = [260 * nblocks + 2 * int(words[c]) if nbins[c] >= 2 else 0 for c in range(ld)]
+        offsets = np.concatenate([[0], np.cumsum([-(-s // 4) * 4 for s in sizes])])
+        out = torch.zeros(max(int(offsets[-1]), 4), dtype=torch.uint8, device=dev)
+        start_dev = torch.from_numpy(np.ascontiguousarray(start)).to(dev)
+        _, _, off_h, words_h = _rans_host_arrays(lo, nbins, offsets[:ld], words)
+        _lib.check(L.shacira_latent_rans_pack(rows, ld, nb_h, steps, _ptr(counts), _ptr(states), _ptr(slots),
+                                              _ptr(start_dev), off_h, words_h, _ptr(out), out.numel(), _stream(latent)),
+                   "shacira_latent_rans_pack")
+        host = out.cpu().numpy()
+    return [host[int(offsets[c]):int(offsets[c]) + sizes[c]].tobytes() for c in range(ld)]
+
+
+def latent_rans_decode(container, rows, ld, lo, nbins, payload_offsets, words, cdf, block_start, steps, device):
+    """Decode a version-2 ("rans64") container on ``device``: fp32 [rows, ld] tensor of symbol + lo.
+
+    ``container``: the container's bytes (uploaded as they are); per channel (host) ``lo``, ``nbins``, byte offset of its
+    payload and number of 16-bit words; ``cdf`` uint32 numpy [ld, stride]; ``block_start`` int64 numpy [ld, nblocks] =
+    exclusive prefix of each channel's per-block word counts. The caller (codec.decompress_latents) has checked the
+    header against the container's size. Raises ValueError when the kernel reports an inconsistent stream."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("shacira_amd: latent_rans_decode runs on the MI355X (HIP) device")
+    out = torch.empty((rows, ld), dtype=torch.float32, device=device)
+    if rows == 0:
+        return out
+    cdf = np.ascontiguousarray(cdf, dtype=np.uint32)
+    L = _lib.lib()
+    with _on_device(device):
+        data = torch.frombuffer(bytearray(container), dtype=torch.uint8).to(device)
+        cdf_dev = torch.from_numpy(cdf.view(np.int32)).to(device)
+        start_dev = torch.from_numpy(np.ascontiguousarray(block_start, dtype=np.int64)).to(device)
+        error = torch.zeros(1, dtype=torch.int32, device=device)
+        lo_h, nb_h, off_h, words_h = _rans_host_arrays(lo, nbins, payload_offsets, words)
+        _lib.check(L.shacira_latent_rans_decode(rows, ld, _ptr(data), data.numel(), lo_h, nb_h, off_h, words_h,
+                                                _ptr(cdf_dev), cdf.shape[1], _ptr(start_dev), int(steps), _ptr(out),
+                                                _ptr(error), _stream(out)), "shacira_latent_rans_decode")
+        if int(error.item()) != 0:
+            raise ValueError("corrupt rans64 payload: the stream does not return to its initial state")
+    return out
 
 
 # ---- triplanes (include/shacira_hip.h, shacira_triplane_*) -----------------------------------------------------------------

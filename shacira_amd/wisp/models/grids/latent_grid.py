@@ -102,17 +102,20 @@ class LatentGrid(_MultiLevelTable):
                 codebook_bits += codec.payload_bits(codec.compress_latents(self.codebook[:, dim:dim + 1]))
         return ldec_size, codebook_bits
 
-    def compress(self) -> bytes:
-        """Entropy-coded container of the rounded latents (what ``size`` estimates), see shacira_amd/codec.py."""
+    def compress(self, coder="range") -> bytes:
+        """Entropy-coded container of the rounded latents (what ``size`` estimates), see shacira_amd/codec.py.
+        ``coder="rans"`` codes a device-resident table with the HIP rANS kernels instead of the host range coder."""
         from .... import codec
-        return codec.compress_latents(self.codebook)
+        return codec.compress_latents(self.codebook, coder=coder)
 
     def load_compressed(self, data: bytes) -> None:
-        """Overwrite the latents with the (integer) values stored by ``compress``."""
+        """Overwrite the latents with the (integer) values stored by ``compress`` (either coder: the container's magic
+        decides; a rANS container decodes on the grid's device)."""
         from .... import codec
+        shape = codec.container_shape(data)                      # from the header: a mismatch decodes (and launches) nothing
+        if shape != tuple(self.codebook.shape):
+            raise ValueError(f"container holds {shape} latents, the grid {tuple(self.codebook.shape)}")
         values = codec.decompress_latents(data, device=self.codebook.device)
-        if tuple(values.shape) != tuple(self.codebook.shape):
-            raise ValueError(f"container holds {tuple(values.shape)} latents, the grid {tuple(self.codebook.shape)}")
         with torch.no_grad():
             self.codebook.copy_(values)
 
