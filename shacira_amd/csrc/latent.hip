@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "internal.h"
+#include "latent_quant.h"
 
 namespace shacira {
 
@@ -114,30 +115,6 @@ struct SgaArgs {
 __device__ __forceinline__ float sga_temperature(const SgaArgs &sga) {
     return sga.temperature_dev ? *sga.temperature_dev : sga.temperature;
 }
-__device__ __forceinline__ void sga_quantise(float w, float u0, float u1, float T, bool diff, float &q, float &dq) {
-    const float lim = 1.0f - 1e-6f, eps = 1.1920929e-07f;
-    const float wf = floorf(w), wc = wf + 1.0f;
-    const float a = w - wf, b = wc - w;
-    const float tf_ = tanhf(fminf(fmaxf(a, -lim), lim)), tc = tanhf(fminf(fmaxf(b, -lim), lim));
-    const float lf = -tf_ / T, lc = -tc / T;
-    u0 = fminf(fmaxf(u0, eps), 1.0f - eps);
-    u1 = fminf(fmaxf(u1, eps), 1.0f - eps);
-    const float z0 = (lf + -logf(-logf(u0))) / T, z1 = (lc + -logf(-logf(u1))) / T;
-    const float m = fmaxf(z0, z1);
-    const float lse = m + logf(expf(z0 - m) + expf(z1 - m));
-    const float s0 = expf(z0 - lse), s1 = expf(z1 - lse);
-    q = wf * s0 + wc * s1;
-    if (diff) {
-        // torch.clamp hands the gradient on at the bounds themselves (w = -0.999999: b == lim)
-        const float in_f = (a >= -lim && a <= lim) ? 1.0f : 0.0f, in_c = (b >= -lim && b <= lim) ? 1.0f : 0.0f;
-        dq = s0 * s1 * ((1.0f - tc * tc) * in_c + (1.0f - tf_ * tf_) * in_f) / (T * T);
-    } else {
-        dq = s0 + s1;
-    }
-}
-
-// torch.clamp(v, -c, c): a NaN stays a NaN (fminf / fmaxf would return the bound)
-__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return v < -c ? -c : (v > c ? c : v); }
 
 template <int LD, int F, bool SGA>
 __device__ __forceinline__ void decode_row(const DecodeConsts<LD, F> &p, const float *__restrict__ latent, int64_t r,
@@ -778,7 +755,7 @@ __global__ __launch_bounds__(kThreads) void entropy_fwd_kernel(const float *__re
             CdfTrace<LD> tp, tn;
             const float prob = cdf_eval<LD, NL>(p, c, w + 0.5f, tp) - cdf_eval<LD, NL>(p, c, w - 0.5f, tn);
             float bits = -__log2f(prob + 1e-10f);      // hardware log2, 1 ulp
-            bits = fminf(fmaxf(bits, 0.0f), 50.0f);
+            bits = bits < 0.0f ? 0.0f : (bits > 50.0f ? 50.0f : bits);   // torch.clamp: a NaN stays a NaN
             acc[0] += bits;
         }
     }

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "internal.h"
+#include "latent_quant.h"
 
 namespace shacira {
 
@@ -25,36 +26,15 @@ constexpr int kLmlpMaxBlocks = 512;
 
 enum Act { kNone = 0, kSigmoid = 1, kTanh = 2, kRelu = 3, kSine = 4 };
 
-// y = act(z), d = act'(z)
+// y = act(z), d = act'(z). ReLU as torch: a NaN pre-activation stays a NaN, and d is 0 where the ACTIVATION is <= 0 (the
+// backward turns that 0 into a select, so a unit that is off gives an exact 0 even under a NaN or infinite gradient).
 __device__ __forceinline__ void activate(int act, float z, float &y, float &d) {
     switch (act) {
     case kSigmoid: y = 1.0f / (1.0f + expf(-z)); d = y * (1.0f - y); break;
     case kTanh: y = tanhf(z); d = 1.0f - y * y; break;
-    case kRelu: y = z > 0.0f ? z : 0.0f; d = z > 0.0f ? 1.0f : 0.0f; break;
+    case kRelu: y = z <= 0.0f ? 0.0f : z; d = y <= 0.0f ? 0.0f : 1.0f; break;
     case kSine: y = sinf(30.0f * z); d = 30.0f * cosf(30.0f * z); break;   // SineScaled(30.0): activations.py
     default: y = z; d = 1.0f; break;
-    }
-}
-
-// same SGA sample as latent.hip (basic_latent_decoder.py:183-191): see sga_quantise there
-__device__ __forceinline__ void sga_sample(float w, float u0, float u1, float T, bool diff, float &q, float &dq) {
-    const float lim = 1.0f - 1e-6f, eps = 1.1920929e-07f;
-    const float wf = floorf(w), wc = wf + 1.0f;
-    const float a = w - wf, b = wc - w;
-    const float tf_ = tanhf(fminf(fmaxf(a, -lim), lim)), tc = tanhf(fminf(fmaxf(b, -lim), lim));
-    const float lf = -tf_ / T, lc = -tc / T;
-    u0 = fminf(fmaxf(u0, eps), 1.0f - eps);
-    u1 = fminf(fmaxf(u1, eps), 1.0f - eps);
-    const float z0 = (lf + -logf(-logf(u0))) / T, z1 = (lc + -logf(-logf(u1))) / T;
-    const float m = fmaxf(z0, z1);
-    const float lse = m + logf(expf(z0 - m) + expf(z1 - m));
-    const float s0 = expf(z0 - lse), s1 = expf(z1 - lse);
-    q = wf * s0 + wc * s1;
-    if (diff) {
-        const float in_f = (a > -lim && a < lim) ? 1.0f : 0.0f, in_c = (b > -lim && b < lim) ? 1.0f : 0.0f;
-        dq = s0 * s1 * ((1.0f - tc * tc) * in_c + (1.0f - tf_ * tf_) * in_f) / (T * T);
-    } else {
-        dq = s0 + s1;
     }
 }
 
@@ -102,7 +82,7 @@ __device__ __forceinline__ void load_row(const MlpLds<W> &s, const MlpShape &sh,
             float q;
             if constexpr (SGA) {
                 const float2 u = *reinterpret_cast<const float2 *>(uniforms + (r * ld + c) * 2);
-                sga_sample(wv, u.x, u.y, T, diff, q, dq[c]);
+                sga_quantise(wv, u.x, u.y, T, diff, q, dq[c]);   // latent_quant.h: the one latent.hip uses
             } else {
                 q = rintf(wv);   // torch.round: half to even; straight-through gradient
                 dq[c] = 1.0f;
@@ -141,11 +121,13 @@ __global__ __launch_bounds__(kLmlpThreads) void latent_mlp_fwd_kernel(MlpShape s
         for (int k = 0; k < SHACIRA_LATENT_MLP_MAX_LAYERS; ++k) {
             if (k < sh.nl) {
                 layer_forward<W>(s.Wm[k], s.b[k], x, z);
-                const int a = (k + 1 < sh.nl) ? sh.act : sh.final_act;
+                const int a = (k + 1 < sh.nl) ? sh.act : sh.final_act, out = sh.w[k + 1];
 #pragma unroll
                 for (int j = 0; j < W; ++j) {
                     float d;
                     activate(a, z[j], x[j], d);
+                    // a padded lane holds fma(x_i, 0, 0): NaN under a non-finite x_i, and NaN * 0 in the next layer
+                    if (j >= out) x[j] = 0.0f;
                 }
             }
         }
@@ -153,7 +135,7 @@ __global__ __launch_bounds__(kLmlpThreads) void latent_mlp_fwd_kernel(MlpShape s
         for (int j = 0; j < W; ++j) {
             if (j < F) {
                 float v = x[j];
-                if (clampw > 0.0f) v = fminf(fmaxf(v, -clampw), clampw);
+                if (clampw > 0.0f) v = clamp_keep_nan(v, clampw);
                 decoded[r * F + j] = v;
             }
         }
@@ -191,11 +173,12 @@ __global__ __launch_bounds__(kLmlpThreads) void latent_mlp_bwd_kernel(MlpShape s
         for (int k = 0; k < NL; ++k) {
             if (k < sh.nl) {
                 layer_forward<W>(s.Wm[k], s.b[k], X[k], z);
-                const int a = (k + 1 < sh.nl) ? sh.act : sh.final_act;
+                const int a = (k + 1 < sh.nl) ? sh.act : sh.final_act, out = sh.w[k + 1];
 #pragma unroll
                 for (int j = 0; j < W; ++j) {
                     float y;
                     activate(a, z[j], y, D[k][j]);
+                    if (j >= out) y = 0.0f;   // padded lane: see the forward kernel
                     if (k + 1 < NL) {
                         if (k + 1 < sh.nl) X[k + 1][j] = y;
                     }
@@ -220,8 +203,14 @@ __global__ __launch_bounds__(kLmlpThreads) void latent_mlp_bwd_kernel(MlpShape s
         for (int kk = 0; kk < NL; ++kk) {
             const int k = NL - 1 - kk;
             if (k < sh.nl) {
+                const bool relu = ((k + 1 < sh.nl) ? sh.act : sh.final_act) == kRelu;
+                const int out = sh.w[k + 1];
 #pragma unroll
-                for (int j = 0; j < W; ++j) G[j] *= D[k][j];
+                for (int j = 0; j < W; ++j) {
+                    // ReLU gates with a select; a padded lane (whose G is a sum of G * 0 of the layer above) carries nothing
+                    const bool off = j >= out || (relu && D[k][j] == 0.0f);
+                    G[j] = off ? 0.0f : G[j] * D[k][j];
+                }
                 // parameter gradients of layer k through LDS: rows of the tile in a fixed order
                 __syncthreads();   // the previous layer's sums are done with s_x / s_g
 #pragma unroll

@@ -689,3 +689,65 @@ def test_entropy_validation_mode_rounds_half_to_even(dev):
         assert lo[r, 0] <= got <= hi[r, 0], (float(lat[r, 0]), got, lo[r, 0], hi[r, 0])
     gl, _ = ops.entropy_bits_backward(_to(dev, lat), None, _to(dev, prm), nl, torch.ones((), device=dev))
     assert float(gl.abs().max()) == 0.0 and not torch.isnan(gl).any()
+
+
+def _torch_entropy(lat, noise, params, nl):
+    """BitEstimator.total_bits on the CPU in float32 (torch ops, autograd): sum clamp(-log2(prob + 1e-10), 0, 50) -> (total,
+    grad_latent, grad_params [4, 3, LD])."""
+    from shacira_amd.wisp.models.prob_models.bit_estimator import BitEstimator
+    ld = lat.shape[1]
+    be = BitEstimator(ld, num_layers=nl)
+    fs = (be.f1, be.f2, be.f3, be.f4)
+    with torch.no_grad():
+        for k, f in enumerate(fs):
+            f.h.copy_(torch.from_numpy(params[k, 0]).view(1, -1))
+            f.b.copy_(torch.from_numpy(params[k, 1]).view(1, -1))
+            if f.a is not None:
+                f.a.copy_(torch.from_numpy(params[k, 2]).view(1, -1))
+    l = torch.from_numpy(lat).requires_grad_(True)
+    tot = be.total_bits(l, None if noise is None else torch.from_numpy(noise))
+    tot.backward()
+    gp = np.zeros((4, 3, ld), np.float32)
+    for k, f in enumerate(fs):
+        for s_, name in enumerate(("h", "b", "a")):
+            prm = getattr(f, name)
+            if prm is not None and prm.grad is not None:
+                gp[k, s_] = prm.grad.numpy().reshape(-1)
+    return float(tot.detach()), l.grad.numpy(), gp
+
+
+@pytest.mark.parametrize("nl,ld,mode", [(2, 1, "latent"), (4, 8, "noise"), (3, 2, "validation")])
+def test_a_nan_latent_or_noise_reaches_the_bits_and_the_gradients_it_feeds(dev, nl, ld, mode):
+    """One NaN (row 255 of 300, the last channel) in the latent, in the noise, or in the latent in validation mode (round()).
+    The policy is float32 torch's own for sum(clamp(-log2(prob + 1e-10), 0, 50)), evaluated here on the CPU and pinned:
+    the total is NaN (torch.clamp keeps a NaN; fminf(fmaxf()) made it 0 bits); grad_latent is NaN at that element and nowhere
+    else (the clamp masks the NaN's gradient to 0, and 0 / NaN in the logarithm's backward is NaN again) -- exactly 0 everywhere
+    in validation mode; the parameter gradients are NaN in every slot of that channel the num_layers chain uses, and in the
+    other channels they equal the run without the NaN bit for bit (each channel has its own accumulators) -- as does
+    grad_latent in every other element."""
+    ops = _ops()
+    rng = np.random.default_rng(nl * 10 + ld)
+    lat = rng.uniform(-8, 8, (300, ld)).astype(np.float32)
+    noise = None if mode == "validation" else rng.uniform(-0.5, 0.5, (300, ld)).astype(np.float32)
+    params = (rng.standard_normal((4, 3, ld)) * 0.4).astype(np.float32)
+    bad_lat, bad_noise = lat.copy(), None if noise is None else noise.copy()
+    (bad_noise if mode == "noise" else bad_lat)[255, ld - 1] = np.nan
+    t_tot, t_gl, t_gp = _torch_entropy(bad_lat, bad_noise, params, nl)
+    used = np.zeros((4, 3, ld), bool)                                   # pinned: what torch makes NaN
+    for k in list(range(nl - 1)) + [3]:
+        used[k, :2 if k == 3 else 3, ld - 1] = True
+    at = np.zeros((300, ld), bool)
+    at[255, ld - 1] = mode != "validation"
+    assert np.isnan(t_tot) and np.array_equal(np.isnan(t_gl), at) and np.array_equal(np.isnan(t_gp), used)
+    if mode == "validation":
+        assert not t_gl.any()
+    gt = torch.ones((), device=dev)
+    run = lambda l_, n_: (float(ops.entropy_bits_forward(_to(dev, l_), _to(dev, n_), _to(dev, params), nl)),) + tuple(
+        x.cpu().numpy() for x in ops.entropy_bits_backward(_to(dev, l_), _to(dev, n_), _to(dev, params), nl, gt))
+    c_tot, c_gl, c_gp = run(lat, noise)
+    tot, gl, gp = run(bad_lat, bad_noise)
+    assert np.isfinite(c_tot) and np.isfinite(c_gl).all() and np.isfinite(c_gp).all()
+    assert np.isnan(tot), tot
+    assert np.array_equal(np.isnan(gl), at) and np.array_equal(gl[~at], c_gl[~at])
+    assert np.array_equal(np.isnan(gp), used), np.argwhere(np.isnan(gp) != used)
+    assert np.array_equal(gp[~used], c_gp[~used])
