@@ -672,17 +672,70 @@ static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_
                                            workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan);
 }
 
+// ---- affine latent decoders: plain, SGA, SGA with the temperature on the device, per-level ---------------------------------
+static int levels_args_ok(int num_levels, const int64_t *row_offsets_host, int64_t num_rows, int latent_dim,
+                          int feature_dim) {
+    if (num_levels < 1 || num_levels > SHACIRA_MAX_LODS || !row_offsets_host) return SHACIRA_EINVAL;
+    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1) return SHACIRA_EINVAL;
+    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
+    int64_t prev = 0;
+    for (int l = 0; l <= num_levels; ++l) {
+        const int64_t o = row_offsets_host[l];
+        if (o < 0 || o > num_rows) return SHACIRA_EINVAL;
+        if (l < num_levels && o < prev) return SHACIRA_EINVAL;   // level starts ascend; the LAST boundary may fall short
+        prev = o;
+    }
+    return 0;
+}
+
+enum DecodeKind { DECODE_ROUND, DECODE_SGA, DECODE_SGA_TDEV, DECODE_LEVELS };
+
+// All eight entry points below; everything but DECODE_LEVELS runs as the one level {0, num_rows} (no offsets). The order of
+// the checks is each entry point's own (it decides which error code a call with several faults gets).
+static int latent_decode_call(bool bwd, DecodeKind kind, int num_levels, const int64_t *row_offsets_host, int64_t num_rows,
+                              int latent_dim, int feature_dim, const float *latent, const float *uniforms, float temperature,
+                              const float *temperature_dev, int diff_sampling, const float *div, const float *matrix,
+                              const float *colscale, const float *shift, float clamp_weights, float *decoded,
+                              const float *grad_decoded, float *grad_latent, float *grad_matrix, float *grad_colscale,
+                              float *grad_shift, void *workspace, size_t workspace_bytes, void *stream) {
+    if (kind == DECODE_LEVELS) {
+        if (int rc = levels_args_ok(num_levels, row_offsets_host, num_rows, latent_dim, feature_dim)) return rc;
+        if (uniforms && !(temperature > 0.0f)) return SHACIRA_EINVAL;
+    } else {
+        if (num_rows < 0 || latent_dim < 1 || feature_dim < 1) return SHACIRA_EINVAL;
+        if (kind == DECODE_SGA && !(temperature > 0.0f)) return SHACIRA_EINVAL;
+        if (kind == DECODE_SGA_TDEV && !temperature_dev) return SHACIRA_EINVAL;
+        if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
+        num_levels = 1;
+        row_offsets_host = nullptr;
+    }
+    if (bwd && (!workspace || workspace_bytes < latent_workspace_bytes())) return SHACIRA_EWORKSPACE;
+    if (!bwd && num_rows == 0) return 0;
+    const bool sga = kind == DECODE_SGA || kind == DECODE_SGA_TDEV;
+    if (num_rows > 0 && (!latent || !div || !matrix || (bwd ? !grad_decoded : !decoded) || (sga && !uniforms)))
+        return SHACIRA_EINVAL;
+    // rows no level owns (before the first level, after the last boundary) decode to 0 and get no gradient
+    float *unowned = bwd ? grad_latent : decoded;
+    if (kind == DECODE_LEVELS && unowned && num_rows > 0) {
+        const size_t n = (size_t)num_rows * (bwd ? latent_dim : feature_dim) * sizeof(float);
+        hipError_t e = hipMemsetAsync(unowned, 0, n, (hipStream_t)stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    DecodeArgs a{};
+    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
+    a.clampw = clamp_weights; a.decoded = decoded; a.grad_decoded = grad_decoded; a.grad_latent = grad_latent;
+    a.grad_matrix = grad_matrix; a.grad_colscale = grad_colscale; a.grad_shift = grad_shift;
+    a.partials = static_cast<double *>(workspace); a.rows = num_rows;
+    a.uniforms = uniforms; a.temperature = temperature; a.temperature_dev = temperature_dev; a.diff_sampling = diff_sampling;
+    return (int)latent_decode_dispatch(bwd, latent_dim, feature_dim, num_levels, row_offsets_host, a, (hipStream_t)stream);
+}
+
 int shacira_latent_decode_forward(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
                                   const float *div, const float *matrix, const float *colscale, const float *shift,
                                   float clamp_weights, float *decoded, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (num_rows == 0) return 0;
-    if (!latent || !div || !matrix || !decoded) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.decoded = decoded; a.rows = num_rows;
-    return (int)latent_decode_dispatch(false, latent_dim, feature_dim, a, (hipStream_t)stream);
+    return latent_decode_call(false, DECODE_ROUND, 1, nullptr, num_rows, latent_dim, feature_dim, latent, nullptr, 0.0f,
+                              nullptr, 0, div, matrix, colscale, shift, clamp_weights, decoded, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, 0, stream);
 }
 
 size_t shacira_latent_decode_backward_workspace_bytes(int64_t, int, int) { return latent_workspace_bytes(); }
@@ -692,16 +745,76 @@ int shacira_latent_decode_backward(int64_t num_rows, int latent_dim, int feature
                                    float clamp_weights, const float *grad_decoded, float *grad_latent,
                                    float *grad_matrix, float *grad_colscale, float *grad_shift, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (!workspace || workspace_bytes < latent_workspace_bytes()) return SHACIRA_EWORKSPACE;
-    if (num_rows > 0 && (!latent || !div || !matrix || !grad_decoded)) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.grad_decoded = grad_decoded; a.grad_latent = grad_latent;
-    a.grad_matrix = grad_matrix; a.grad_colscale = grad_colscale; a.grad_shift = grad_shift;
-    a.partials = static_cast<double *>(workspace); a.rows = num_rows;
-    return (int)latent_decode_dispatch(true, latent_dim, feature_dim, a, (hipStream_t)stream);
+    return latent_decode_call(true, DECODE_ROUND, 1, nullptr, num_rows, latent_dim, feature_dim, latent, nullptr, 0.0f,
+                              nullptr, 0, div, matrix, colscale, shift, clamp_weights, nullptr, grad_decoded, grad_latent,
+                              grad_matrix, grad_colscale, grad_shift, workspace, workspace_bytes, stream);
+}
+
+int shacira_latent_decode_sga_forward(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
+                                      const float *uniforms, float temperature, int diff_sampling, const float *div,
+                                      const float *matrix, const float *colscale, const float *shift,
+                                      float clamp_weights, float *decoded, void *stream) {
+    return latent_decode_call(false, DECODE_SGA, 1, nullptr, num_rows, latent_dim, feature_dim, latent, uniforms,
+                              temperature, nullptr, diff_sampling, div, matrix, colscale, shift, clamp_weights, decoded,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int shacira_latent_decode_sga_backward(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
+                                       const float *uniforms, float temperature, int diff_sampling, const float *div,
+                                       const float *matrix, const float *colscale, const float *shift,
+                                       float clamp_weights, const float *grad_decoded, float *grad_latent,
+                                       float *grad_matrix, float *grad_colscale, float *grad_shift, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    return latent_decode_call(true, DECODE_SGA, 1, nullptr, num_rows, latent_dim, feature_dim, latent, uniforms,
+                              temperature, nullptr, diff_sampling, div, matrix, colscale, shift, clamp_weights, nullptr,
+                              grad_decoded, grad_latent, grad_matrix, grad_colscale, grad_shift, workspace,
+                              workspace_bytes, stream);
+}
+
+// The same pair with the temperature in DEVICE memory (one float, read by the kernels): a training step captured into a HIP
+// graph anneals the temperature between replays (base_trainer.py:155-157 decays it every iteration) without re-capturing.
+int shacira_latent_decode_sga_forward_tdev(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
+                                           const float *uniforms, const float *temperature_dev, int diff_sampling,
+                                           const float *div, const float *matrix, const float *colscale, const float *shift,
+                                           float clamp_weights, float *decoded, void *stream) {
+    return latent_decode_call(false, DECODE_SGA_TDEV, 1, nullptr, num_rows, latent_dim, feature_dim, latent, uniforms, 1.0f,
+                              temperature_dev, diff_sampling, div, matrix, colscale, shift, clamp_weights, decoded, nullptr,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int shacira_latent_decode_sga_backward_tdev(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
+                                            const float *uniforms, const float *temperature_dev, int diff_sampling,
+                                            const float *div, const float *matrix, const float *colscale, const float *shift,
+                                            float clamp_weights, const float *grad_decoded, float *grad_latent,
+                                            float *grad_matrix, float *grad_colscale, float *grad_shift, void *workspace,
+                                            size_t workspace_bytes, void *stream) {
+    return latent_decode_call(true, DECODE_SGA_TDEV, 1, nullptr, num_rows, latent_dim, feature_dim, latent, uniforms, 1.0f,
+                              temperature_dev, diff_sampling, div, matrix, colscale, shift, clamp_weights, nullptr,
+                              grad_decoded, grad_latent, grad_matrix, grad_colscale, grad_shift, workspace,
+                              workspace_bytes, stream);
+}
+
+int shacira_latent_decode_levels_forward(int num_levels, const int64_t *row_offsets_host, int64_t num_rows,
+                                         int latent_dim, int feature_dim, const float *latent, const float *uniforms,
+                                         float temperature, int diff_sampling, const float *div, const float *matrix,
+                                         const float *colscale, const float *shift, float clamp_weights, float *decoded,
+                                         void *stream) {
+    return latent_decode_call(false, DECODE_LEVELS, num_levels, row_offsets_host, num_rows, latent_dim, feature_dim, latent,
+                              uniforms, temperature, nullptr, diff_sampling, div, matrix, colscale, shift, clamp_weights,
+                              decoded, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int shacira_latent_decode_levels_backward(int num_levels, const int64_t *row_offsets_host, int64_t num_rows,
+                                          int latent_dim, int feature_dim, const float *latent, const float *uniforms,
+                                          float temperature, int diff_sampling, const float *div, const float *matrix,
+                                          const float *colscale, const float *shift, float clamp_weights,
+                                          const float *grad_decoded, float *grad_latent, float *grad_matrix,
+                                          float *grad_colscale, float *grad_shift, void *workspace,
+                                          size_t workspace_bytes, void *stream) {
+    return latent_decode_call(true, DECODE_LEVELS, num_levels, row_offsets_host, num_rows, latent_dim, feature_dim, latent,
+                              uniforms, temperature, nullptr, diff_sampling, div, matrix, colscale, shift, clamp_weights,
+                              nullptr, grad_decoded, grad_latent, grad_matrix, grad_colscale, grad_shift, workspace,
+                              workspace_bytes, stream);
 }
 
 int shacira_latent_mlp_supported(int num_layers, const int32_t *widths_host) {
@@ -757,136 +870,6 @@ int shacira_latent_mlp_backward(int64_t num_rows, int num_layers, const int32_t 
                            workspace, workspace_bytes, stream);
 }
 
-int shacira_latent_decode_sga_forward(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
-                                      const float *uniforms, float temperature, int diff_sampling, const float *div,
-                                      const float *matrix, const float *colscale, const float *shift,
-                                      float clamp_weights, float *decoded, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1 || !(temperature > 0.0f)) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (num_rows == 0) return 0;
-    if (!latent || !uniforms || !div || !matrix || !decoded) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.decoded = decoded; a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = temperature; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_dispatch(false, latent_dim, feature_dim, a, (hipStream_t)stream);
-}
-
-int shacira_latent_decode_sga_backward(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
-                                       const float *uniforms, float temperature, int diff_sampling, const float *div,
-                                       const float *matrix, const float *colscale, const float *shift,
-                                       float clamp_weights, const float *grad_decoded, float *grad_latent,
-                                       float *grad_matrix, float *grad_colscale, float *grad_shift, void *workspace,
-                                       size_t workspace_bytes, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1 || !(temperature > 0.0f)) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (!workspace || workspace_bytes < latent_workspace_bytes()) return SHACIRA_EWORKSPACE;
-    if (num_rows > 0 && (!latent || !uniforms || !div || !matrix || !grad_decoded)) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.grad_decoded = grad_decoded; a.grad_latent = grad_latent;
-    a.grad_matrix = grad_matrix; a.grad_colscale = grad_colscale; a.grad_shift = grad_shift;
-    a.partials = static_cast<double *>(workspace); a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = temperature; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_dispatch(true, latent_dim, feature_dim, a, (hipStream_t)stream);
-}
-
-// The same pair with the temperature in DEVICE memory (one float, read by the kernels): a training step captured into a HIP
-// graph anneals the temperature between replays (base_trainer.py:155-157 decays it every iteration) without re-capturing.
-int shacira_latent_decode_sga_forward_tdev(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
-                                           const float *uniforms, const float *temperature_dev, int diff_sampling,
-                                           const float *div, const float *matrix, const float *colscale, const float *shift,
-                                           float clamp_weights, float *decoded, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1 || !temperature_dev) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (num_rows == 0) return 0;
-    if (!latent || !uniforms || !div || !matrix || !decoded) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.decoded = decoded; a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = 1.0f; a.temperature_dev = temperature_dev; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_dispatch(false, latent_dim, feature_dim, a, (hipStream_t)stream);
-}
-
-int shacira_latent_decode_sga_backward_tdev(int64_t num_rows, int latent_dim, int feature_dim, const float *latent,
-                                            const float *uniforms, const float *temperature_dev, int diff_sampling,
-                                            const float *div, const float *matrix, const float *colscale, const float *shift,
-                                            float clamp_weights, const float *grad_decoded, float *grad_latent,
-                                            float *grad_matrix, float *grad_colscale, float *grad_shift, void *workspace,
-                                            size_t workspace_bytes, void *stream) {
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1 || !temperature_dev) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    if (!workspace || workspace_bytes < latent_workspace_bytes()) return SHACIRA_EWORKSPACE;
-    if (num_rows > 0 && (!latent || !uniforms || !div || !matrix || !grad_decoded)) return SHACIRA_EINVAL;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.grad_decoded = grad_decoded; a.grad_latent = grad_latent;
-    a.grad_matrix = grad_matrix; a.grad_colscale = grad_colscale; a.grad_shift = grad_shift;
-    a.partials = static_cast<double *>(workspace); a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = 1.0f; a.temperature_dev = temperature_dev; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_dispatch(true, latent_dim, feature_dim, a, (hipStream_t)stream);
-}
-
-static int levels_args_ok(int num_levels, const int64_t *row_offsets_host, int64_t num_rows, int latent_dim,
-                          int feature_dim) {
-    if (num_levels < 1 || num_levels > SHACIRA_MAX_LODS || !row_offsets_host) return SHACIRA_EINVAL;
-    if (num_rows < 0 || latent_dim < 1 || feature_dim < 1) return SHACIRA_EINVAL;
-    if (!latent_decode_supported(latent_dim, feature_dim)) return SHACIRA_EDTYPE;
-    int64_t prev = 0;
-    for (int l = 0; l <= num_levels; ++l) {
-        const int64_t o = row_offsets_host[l];
-        if (o < 0 || o > num_rows) return SHACIRA_EINVAL;
-        if (l < num_levels && o < prev) return SHACIRA_EINVAL;   // level starts ascend; the LAST boundary may fall short
-        prev = o;
-    }
-    return 0;
-}
-
-int shacira_latent_decode_levels_forward(int num_levels, const int64_t *row_offsets_host, int64_t num_rows,
-                                         int latent_dim, int feature_dim, const float *latent, const float *uniforms,
-                                         float temperature, int diff_sampling, const float *div, const float *matrix,
-                                         const float *colscale, const float *shift, float clamp_weights, float *decoded,
-                                         void *stream) {
-    if (int rc = levels_args_ok(num_levels, row_offsets_host, num_rows, latent_dim, feature_dim)) return rc;
-    if (uniforms && !(temperature > 0.0f)) return SHACIRA_EINVAL;
-    if (num_rows == 0) return 0;
-    if (!latent || !div || !matrix || !decoded) return SHACIRA_EINVAL;
-    // rows no level owns (before the first level, after the last boundary) decode to 0
-    hipError_t e = hipMemsetAsync(decoded, 0, (size_t)num_rows * feature_dim * sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.decoded = decoded; a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = temperature; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_levels_dispatch(false, latent_dim, feature_dim, num_levels, row_offsets_host, a,
-                                              (hipStream_t)stream);
-}
-
-int shacira_latent_decode_levels_backward(int num_levels, const int64_t *row_offsets_host, int64_t num_rows,
-                                          int latent_dim, int feature_dim, const float *latent, const float *uniforms,
-                                          float temperature, int diff_sampling, const float *div, const float *matrix,
-                                          const float *colscale, const float *shift, float clamp_weights,
-                                          const float *grad_decoded, float *grad_latent, float *grad_matrix,
-                                          float *grad_colscale, float *grad_shift, void *workspace,
-                                          size_t workspace_bytes, void *stream) {
-    if (int rc = levels_args_ok(num_levels, row_offsets_host, num_rows, latent_dim, feature_dim)) return rc;
-    if (uniforms && !(temperature > 0.0f)) return SHACIRA_EINVAL;
-    if (!workspace || workspace_bytes < latent_workspace_bytes()) return SHACIRA_EWORKSPACE;
-    if (num_rows > 0 && (!latent || !div || !matrix || !grad_decoded)) return SHACIRA_EINVAL;
-    if (grad_latent && num_rows > 0) {
-        hipError_t e = hipMemsetAsync(grad_latent, 0, (size_t)num_rows * latent_dim * sizeof(float), (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    DecodeArgs a{};
-    a.latent = latent; a.div = div; a.matrix = matrix; a.colscale = colscale; a.shift = shift;
-    a.clampw = clamp_weights; a.grad_decoded = grad_decoded; a.grad_latent = grad_latent;
-    a.grad_matrix = grad_matrix; a.grad_colscale = grad_colscale; a.grad_shift = grad_shift;
-    a.partials = static_cast<double *>(workspace); a.rows = num_rows;
-    a.uniforms = uniforms; a.temperature = temperature; a.diff_sampling = diff_sampling;
-    return (int)latent_decode_levels_dispatch(true, latent_dim, feature_dim, num_levels, row_offsets_host, a,
-                                              (hipStream_t)stream);
-}
-
 int shacira_latent_multi_supported(int latent_dim, int feature_dim, int num_decoders) {
     return latent_multi_supported(latent_dim, feature_dim, num_decoders) ? 1 : 0;
 }
@@ -905,10 +888,11 @@ int shacira_latent_multi_decode_forward(int64_t num_rows, int latent_dim, int fe
     if (int rc = multi_args_ok(num_rows, latent_dim, feature_dim, num_decoders, temperature)) return rc;
     if (num_rows == 0) return 0;
     if (!latent || !alpha || !div || !scale || !decoded) return SHACIRA_EINVAL;
-    return (int)latent_multi_dispatch(false, latent_dim, feature_dim, dft != nullptr, latent, alpha, num_decoders, uniforms,
-                                      temperature, straight_through, diff_sampling, div, scale, dft, shift, clamp_weights,
-                                      num_rows, decoded, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      (hipStream_t)stream);
+    MultiArgs a{};
+    a.latent = latent; a.alpha = alpha; a.div = div; a.scale = scale; a.dft = dft; a.shift = shift; a.uniforms = uniforms;
+    a.decoded = decoded; a.rows = num_rows; a.K = num_decoders; a.straight_through = straight_through;
+    a.diff_sampling = diff_sampling; a.temperature = temperature; a.clampw = clamp_weights;
+    return (int)latent_multi_dispatch(false, latent_dim, feature_dim, dft != nullptr, a, (hipStream_t)stream);
 }
 
 int shacira_latent_multi_decode_backward(int64_t num_rows, int latent_dim, int feature_dim, int num_decoders,
@@ -921,10 +905,13 @@ int shacira_latent_multi_decode_backward(int64_t num_rows, int latent_dim, int f
     if (int rc = multi_args_ok(num_rows, latent_dim, feature_dim, num_decoders, temperature)) return rc;
     if (!workspace || workspace_bytes < latent_workspace_bytes()) return SHACIRA_EWORKSPACE;
     if (!grad_scale || (num_rows > 0 && (!latent || !alpha || !div || !scale || !grad_decoded))) return SHACIRA_EINVAL;
-    return (int)latent_multi_dispatch(true, latent_dim, feature_dim, dft != nullptr, latent, alpha, num_decoders, uniforms,
-                                      temperature, straight_through, diff_sampling, div, scale, dft, shift, clamp_weights,
-                                      num_rows, nullptr, grad_decoded, grad_latent, grad_alpha, grad_scale, grad_shift,
-                                      static_cast<double *>(workspace), (hipStream_t)stream);
+    MultiArgs a{};
+    a.latent = latent; a.alpha = alpha; a.div = div; a.scale = scale; a.dft = dft; a.shift = shift; a.uniforms = uniforms;
+    a.grad_decoded = grad_decoded; a.grad_latent = grad_latent; a.grad_alpha = grad_alpha; a.grad_scale = grad_scale;
+    a.grad_shift = grad_shift; a.partials = static_cast<double *>(workspace); a.rows = num_rows; a.K = num_decoders;
+    a.straight_through = straight_through; a.diff_sampling = diff_sampling; a.temperature = temperature;
+    a.clampw = clamp_weights;
+    return (int)latent_multi_dispatch(true, latent_dim, feature_dim, dft != nullptr, a, (hipStream_t)stream);
 }
 
 int shacira_latent_symbol_range(int64_t num_rows, int latent_dim, const float *latent, int32_t *minmax, void *stream) {

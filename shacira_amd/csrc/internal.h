@@ -185,6 +185,14 @@ struct DecodeArgs {
     int diff_sampling;
     const float *temperature_dev;   // non-NULL: SGA temperature read on the device (single / per-level decoders)
 };
+struct MultiArgs {   // passed to multi_decode_kernel by value
+    const float *latent, *alpha, *div, *scale, *dft, *shift, *uniforms, *grad_decoded;
+    float *decoded, *grad_latent, *grad_alpha, *grad_scale, *grad_shift;
+    double *partials;
+    int64_t rows;
+    int K, straight_through, diff_sampling;
+    float temperature, clampw;
+};
 struct EntropyArgs {
     const float *latent, *noise, *params, *grad_total;
     int num_layers;
@@ -212,16 +220,12 @@ hipError_t latent_mlp_dispatch(bool bwd, const LatentMlpArgs &a, hipStream_t s);
 
 size_t latent_workspace_bytes();
 bool latent_decode_supported(int ld, int f);
-hipError_t latent_decode_dispatch(bool bwd, int ld, int f, const DecodeArgs &a, hipStream_t s);
-hipError_t latent_decode_levels_dispatch(bool bwd, int ld, int f, int levels, const int64_t *offsets,
-                                         const DecodeArgs &a, hipStream_t s);
+// level l owns rows [offsets[l], offsets[l + 1]) (host array of levels + 1); offsets == NULL: the plain decoder, which is the
+// one level {0, a.rows}
+hipError_t latent_decode_dispatch(bool bwd, int ld, int f, int levels, const int64_t *offsets, const DecodeArgs &a,
+                                  hipStream_t s);
 bool latent_multi_supported(int ld, int f, int K);
-hipError_t latent_multi_dispatch(bool bwd, int ld, int f, bool dft, const float *latent, const float *alpha, int K,
-                                 const float *uniforms, float temperature, int straight_through, int diff_sampling,
-                                 const float *div, const float *scale, const float *dftm, const float *shift,
-                                 float clampw, int64_t rows, float *decoded, const float *grad_decoded,
-                                 float *grad_latent, float *grad_alpha, float *grad_scale, float *grad_shift,
-                                 double *partials, hipStream_t s);
+hipError_t latent_multi_dispatch(bool bwd, int ld, int f, bool dft, const MultiArgs &a, hipStream_t s);
 bool entropy_supported(int ld);
 hipError_t entropy_dispatch(bool bwd, int ld, const EntropyArgs &a, hipStream_t s);
 

@@ -8,6 +8,12 @@
 // kept as fp64 block partials (workspace) and finished by one small kernel, so they are bitwise reproducible.
 //
 // The tiny per-channel parameter vectors are read through uniform (scalar) loads from their device pointers.
+//
+// The affine decoders share ONE row loop each way, in per-level form (grid.y = level, row range [lo[l], lo[l+1]), partials
+// [level][block][NRED]), one launcher and one dispatch table; the plain, SGA and device-temperature decoders are the single
+// level {0, rows}, with the block count grid_for(rows) they always had. In the backward that level has a kernel entry of its
+// own, without the 264-byte LevelRows argument, which cost 0.3 us per launch there and nothing measurable in the forward
+// (profiles/latent_decode_unify.md). finish_partials_kernel takes grid (nred, levels) for every caller.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,17 +53,18 @@ __device__ __forceinline__ void block_reduce_store(const float (&acc)[NRED], dou
     }
 }
 
-// out[q] = scale * sum_b partials[b][q]; one workgroup per q (fixed summation tree -> bitwise reproducible).
-// The nred results are split over up to three fp32 outputs (NULL = skip).
+// out[l][q] = scale * sum_b partials[l][b][q]; grid = (nred, levels), one workgroup per value (fixed summation tree ->
+// bitwise reproducible). The nred results of a level are split over up to three fp32 outputs (NULL = skip); scale: NULL = 1.
 __global__ __launch_bounds__(256) void finish_partials_kernel(const double *__restrict__ partials, int nblocks,
                                                               int nred, const float *__restrict__ scale,
                                                               float *__restrict__ out0, int n0,
                                                               float *__restrict__ out1, int n1,
                                                               float *__restrict__ out2, int n2) {
     __shared__ double s_w[4];
-    const int q = blockIdx.x;
+    const int q = blockIdx.x, l = blockIdx.y;
+    const double *pl = partials + (size_t)l * nblocks * nred;
     double v = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) v += partials[(size_t)b * nred + q];
+    for (int b = threadIdx.x; b < nblocks; b += 256) v += pl[(size_t)b * nred + q];
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -65,11 +72,11 @@ __global__ __launch_bounds__(256) void finish_partials_kernel(const double *__re
         v = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
         if (scale) v *= (double)scale[0];
         if (q < n0) {
-            if (out0) out0[q] = (float)v;
+            if (out0) out0[(size_t)l * n0 + q] = (float)v;
         } else if (q < n0 + n1) {
-            if (out1) out1[q - n0] = (float)v;
+            if (out1) out1[(size_t)l * n1 + (q - n0)] = (float)v;
         } else if (q < n0 + n1 + n2) {
-            if (out2) out2[q - n0 - n1] = (float)v;
+            if (out2) out2[(size_t)l * n2 + (q - n0 - n1)] = (float)v;
         }
     }
 }
@@ -142,15 +149,26 @@ __device__ __forceinline__ void decode_row(const DecodeConsts<LD, F> &p, const f
     }
 }
 
+// Per-level decoders (HierarchicalLatentDecoder, reference hierarchical_latent_decoder.py:3-36 with the offsets of
+// latent_grid.py:176-190): level l owns rows [lo[l], lo[l+1]) and has its own div / matrix / colscale / shift. ONE launch:
+// grid.y = level, the level's parameters are rows of stacked arrays. The reference runs num_lods decoders (each the
+// ~10-kernel ATen chain) and a torch.cat. The plain decoder is the one-level case {0, rows}.
+struct LevelRows {
+    int64_t lo[SHACIRA_MAX_LODS + 1];
+};
+
 template <int LD, int F, bool SGA>
 __global__ __launch_bounds__(kThreads) void latent_decode_fwd_kernel(
-    const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
+    LevelRows lr, const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
     const float *__restrict__ colscale, const float *__restrict__ shift, float clampw, float *__restrict__ decoded,
-    int64_t rows, SgaArgs sga) {
+    SgaArgs sga) {
+    const int l = blockIdx.y;
+    const int64_t lo = lr.lo[l], hi = lr.lo[l + 1];
     DecodeConsts<LD, F> p;
-    p.load(div, matrix, colscale, shift, clampw);
+    p.load(div + l * LD, matrix + l * LD * F, colscale ? colscale + l * F : nullptr, shift ? shift + l * F : nullptr,
+           clampw);
     const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < rows; r += stride) {
+    for (int64_t r = lo + (int64_t)blockIdx.x * kThreads + threadIdx.x; r < hi; r += stride) {
         float z[LD], dq[LD], zm[F], y[F];
         decode_row<LD, F, SGA>(p, latent, r, sga, z, dq, zm, y);
 #pragma unroll
@@ -164,19 +182,21 @@ __global__ __launch_bounds__(kThreads) void latent_decode_fwd_kernel(
 
 // reductions: [LD*F] grad_matrix, [F] grad_colscale, [F] grad_shift
 template <int LD, int F, bool SGA>
-__global__ __launch_bounds__(kThreads) void latent_decode_bwd_kernel(
-    const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
-    const float *__restrict__ colscale, const float *__restrict__ shift, float clampw,
-    const float *__restrict__ grad_decoded, float *__restrict__ grad_latent, double *__restrict__ partials,
-    int64_t rows, SgaArgs sga) {
+__device__ __forceinline__ void decode_bwd_rows(int l, int64_t lo, int64_t hi, const float *__restrict__ latent,
+                                                const float *__restrict__ div, const float *__restrict__ matrix,
+                                                const float *__restrict__ colscale, const float *__restrict__ shift,
+                                                float clampw, const float *__restrict__ grad_decoded,
+                                                float *__restrict__ grad_latent, double *__restrict__ partials,
+                                                const SgaArgs &sga) {
     constexpr int NRED = LD * F + 2 * F;
     DecodeConsts<LD, F> p;
-    p.load(div, matrix, colscale, shift, clampw);
+    p.load(div + l * LD, matrix + l * LD * F, colscale ? colscale + l * F : nullptr, shift ? shift + l * F : nullptr,
+           clampw);
     float acc[NRED];
 #pragma unroll
     for (int q = 0; q < NRED; ++q) acc[q] = 0.0f;
     const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < rows; r += stride) {
+    for (int64_t r = lo + (int64_t)blockIdx.x * kThreads + threadIdx.x; r < hi; r += stride) {
         float z[LD], dq[LD], zm[F], y[F], gy[F];
         decode_row<LD, F, SGA>(p, latent, r, sga, z, dq, zm, y);
 #pragma unroll
@@ -200,142 +220,49 @@ __global__ __launch_bounds__(kThreads) void latent_decode_bwd_kernel(
             if (grad_latent) grad_latent[r * LD + c] = gl / p.div[c] * dq[c];  // dq = 1: straight-through rounding
         }
     }
-    block_reduce_store<NRED>(acc, partials);
-}
-
-template <int LD, int F> static hipError_t decode_launch(bool bwd, const DecodeArgs &a, hipStream_t s) {
-    const int blocks = grid_for(a.rows);
-    const SgaArgs sga{a.uniforms, a.temperature, a.diff_sampling, a.temperature_dev};
-    if (!bwd) {
-        if (a.uniforms)
-            hipLaunchKernelGGL((latent_decode_fwd_kernel<LD, F, true>), dim3(blocks), dim3(kThreads), 0, s, a.latent,
-                               a.div, a.matrix, a.colscale, a.shift, a.clampw, a.decoded, a.rows, sga);
-        else
-            hipLaunchKernelGGL((latent_decode_fwd_kernel<LD, F, false>), dim3(blocks), dim3(kThreads), 0, s, a.latent,
-                               a.div, a.matrix, a.colscale, a.shift, a.clampw, a.decoded, a.rows, sga);
-        return hipGetLastError();
-    }
-    if (a.uniforms)
-        hipLaunchKernelGGL((latent_decode_bwd_kernel<LD, F, true>), dim3(blocks), dim3(kThreads), 0, s, a.latent, a.div,
-                           a.matrix, a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials, a.rows,
-                           sga);
-    else
-        hipLaunchKernelGGL((latent_decode_bwd_kernel<LD, F, false>), dim3(blocks), dim3(kThreads), 0, s, a.latent,
-                           a.div, a.matrix, a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials,
-                           a.rows, sga);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(finish_partials_kernel, dim3(LD * F + 2 * F), dim3(256), 0, s, a.partials, blocks,
-                       LD * F + 2 * F, (const float *)nullptr, a.grad_matrix, LD * F, a.grad_colscale, F, a.grad_shift,
-                       F);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Per-level decoders (HierarchicalLatentDecoder, reference hierarchical_latent_decoder.py:3-36 with the offsets of
-// latent_grid.py:176-190): level l owns rows [lo[l], lo[l+1]) and has its own div / matrix / colscale / shift. ONE launch:
-// grid.y = level, the level's parameters are rows of stacked arrays. The reference runs num_lods decoders (each the
-// ~10-kernel ATen chain) and a torch.cat.
-struct LevelRows {
-    int64_t lo[SHACIRA_MAX_LODS + 1];
-};
-
-template <int LD, int F, bool SGA>
-__global__ __launch_bounds__(kThreads) void latent_decode_levels_fwd_kernel(
-    LevelRows lr, const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
-    const float *__restrict__ colscale, const float *__restrict__ shift, float clampw, float *__restrict__ decoded,
-    SgaArgs sga) {
-    const int l = blockIdx.y;
-    const int64_t lo = lr.lo[l], hi = lr.lo[l + 1];
-    DecodeConsts<LD, F> p;
-    p.load(div + l * LD, matrix + l * LD * F, colscale ? colscale + l * F : nullptr, shift ? shift + l * F : nullptr,
-           clampw);
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t r = lo + (int64_t)blockIdx.x * kThreads + threadIdx.x; r < hi; r += stride) {
-        float z[LD], dq[LD], zm[F], y[F];
-        decode_row<LD, F, SGA>(p, latent, r, sga, z, dq, zm, y);
-#pragma unroll
-        for (int j = 0; j < F; ++j) {
-            float v = y[j];
-            if (clampw > 0.0f) v = clamp_keep_nan(v, clampw);
-            decoded[r * F + j] = v;
-        }
-    }
-}
-
-template <int LD, int F, bool SGA>
-__global__ __launch_bounds__(kThreads) void latent_decode_levels_bwd_kernel(
-    LevelRows lr, const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
-    const float *__restrict__ colscale, const float *__restrict__ shift, float clampw,
-    const float *__restrict__ grad_decoded, float *__restrict__ grad_latent, double *__restrict__ partials,
-    SgaArgs sga) {
-    constexpr int NRED = LD * F + 2 * F;
-    const int l = blockIdx.y;
-    const int64_t lo = lr.lo[l], hi = lr.lo[l + 1];
-    DecodeConsts<LD, F> p;
-    p.load(div + l * LD, matrix + l * LD * F, colscale ? colscale + l * F : nullptr, shift ? shift + l * F : nullptr,
-           clampw);
-    float acc[NRED];
-#pragma unroll
-    for (int q = 0; q < NRED; ++q) acc[q] = 0.0f;
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t r = lo + (int64_t)blockIdx.x * kThreads + threadIdx.x; r < hi; r += stride) {
-        float z[LD], dq[LD], zm[F], y[F], gy[F];
-        decode_row<LD, F, SGA>(p, latent, r, sga, z, dq, zm, y);
-#pragma unroll
-        for (int j = 0; j < F; ++j) {
-            float g = grad_decoded[r * F + j];
-            if (clampw > 0.0f && !(y[j] >= -clampw && y[j] <= clampw)) g = 0.0f;
-            gy[j] = g;
-            acc[LD * F + j] += g * zm[j];
-            acc[LD * F + F + j] += g;
-        }
-#pragma unroll
-        for (int c = 0; c < LD; ++c) {
-            float gl = 0.0f;
-#pragma unroll
-            for (int j = 0; j < F; ++j) {
-                const float gs = gy[j] * p.cs[j];
-                acc[c * F + j] += z[c] * gs;
-                gl = fmaf(gs, p.mat[c * F + j], gl);
-            }
-            if (grad_latent) grad_latent[r * LD + c] = gl / p.div[c] * dq[c];
-        }
-    }
     // partials[level][block][NRED]
     block_reduce_store<NRED>(acc, partials + (size_t)l * gridDim.x * NRED);
 }
 
-// per level: out[l][q] = sum_b partials[l][b][q]; grid = (nred, levels)
-__global__ __launch_bounds__(256) void finish_level_partials_kernel(const double *__restrict__ partials, int nblocks,
-                                                                    int nred, float *__restrict__ out0, int n0,
-                                                                    float *__restrict__ out1, int n1,
-                                                                    float *__restrict__ out2, int n2) {
-    __shared__ double s_w[4];
-    const int q = blockIdx.x, l = blockIdx.y;
-    const double *pl = partials + (size_t)l * nblocks * nred;
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) v += pl[(size_t)b * nred + q];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        v = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-        if (q < n0) {
-            if (out0) out0[(size_t)l * n0 + q] = (float)v;
-        } else if (q < n0 + n1) {
-            if (out1) out1[(size_t)l * n1 + (q - n0)] = (float)v;
-        } else if (q < n0 + n1 + n2) {
-            if (out2) out2[(size_t)l * n2 + (q - n0 - n1)] = (float)v;
-        }
-    }
+template <int LD, int F, bool SGA>
+__global__ __launch_bounds__(kThreads) void latent_decode_bwd_kernel(
+    LevelRows lr, const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
+    const float *__restrict__ colscale, const float *__restrict__ shift, float clampw,
+    const float *__restrict__ grad_decoded, float *__restrict__ grad_latent, double *__restrict__ partials,
+    SgaArgs sga) {
+    const int l = blockIdx.y;
+    decode_bwd_rows<LD, F, SGA>(l, lr.lo[l], lr.lo[l + 1], latent, div, matrix, colscale, shift, clampw, grad_decoded,
+                                grad_latent, partials, sga);
+}
+
+template <int LD, int F, bool SGA>
+__global__ __launch_bounds__(kThreads) void latent_decode_bwd1_kernel(
+    const float *__restrict__ latent, const float *__restrict__ div, const float *__restrict__ matrix,
+    const float *__restrict__ colscale, const float *__restrict__ shift, float clampw,
+    const float *__restrict__ grad_decoded, float *__restrict__ grad_latent, double *__restrict__ partials, int64_t rows,
+    SgaArgs sga) {
+    decode_bwd_rows<LD, F, SGA>(0, 0, rows, latent, div, matrix, colscale, shift, clampw, grad_decoded, grad_latent,
+                                partials, sga);
+}
+
+template <int LD, int F, bool SGA>
+static void decode_bwd_launch(dim3 grid, bool plain, const LevelRows &lr, const DecodeArgs &a, const SgaArgs &sga,
+                              hipStream_t s) {
+    if (plain)
+        hipLaunchKernelGGL((latent_decode_bwd1_kernel<LD, F, SGA>), grid, dim3(kThreads), 0, s, a.latent, a.div, a.matrix,
+                           a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials, lr.lo[1], sga);
+    else
+        hipLaunchKernelGGL((latent_decode_bwd_kernel<LD, F, SGA>), grid, dim3(kThreads), 0, s, lr, a.latent, a.div,
+                           a.matrix, a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials, sga);
 }
 
 template <int LD, int F>
-static hipError_t decode_levels_launch(bool bwd, int levels, const int64_t *offsets, const DecodeArgs &a, hipStream_t s) {
+static hipError_t decode_launch(bool bwd, int levels, const int64_t *offsets, const DecodeArgs &a, hipStream_t s) {
+    const bool plain = offsets == nullptr;   // the one level {0, a.rows}; its backward has the entry without LevelRows
     LevelRows lr{};
     int64_t longest = 0;
-    for (int l = 0; l <= levels; ++l) lr.lo[l] = offsets[l];
+    if (plain) lr.lo[1] = a.rows;
+    for (int l = 0; l <= levels && !plain; ++l) lr.lo[l] = offsets[l];
     for (int l = 0; l < levels; ++l) {
         if (lr.lo[l + 1] < lr.lo[l]) lr.lo[l + 1] = lr.lo[l];   // empty level (the reference's last-offset quirk)
         if (lr.lo[l + 1] - lr.lo[l] > longest) longest = lr.lo[l + 1] - lr.lo[l];
@@ -347,27 +274,22 @@ static hipError_t decode_levels_launch(bool bwd, int levels, const int64_t *offs
     const dim3 grid(blocks, levels);
     if (!bwd) {
         if (a.uniforms)
-            hipLaunchKernelGGL((latent_decode_levels_fwd_kernel<LD, F, true>), grid, dim3(kThreads), 0, s, lr, a.latent,
-                               a.div, a.matrix, a.colscale, a.shift, a.clampw, a.decoded, sga);
+            hipLaunchKernelGGL((latent_decode_fwd_kernel<LD, F, true>), grid, dim3(kThreads), 0, s, lr, a.latent, a.div,
+                               a.matrix, a.colscale, a.shift, a.clampw, a.decoded, sga);
         else
-            hipLaunchKernelGGL((latent_decode_levels_fwd_kernel<LD, F, false>), grid, dim3(kThreads), 0, s, lr, a.latent,
-                               a.div, a.matrix, a.colscale, a.shift, a.clampw, a.decoded, sga);
+            hipLaunchKernelGGL((latent_decode_fwd_kernel<LD, F, false>), grid, dim3(kThreads), 0, s, lr, a.latent, a.div,
+                               a.matrix, a.colscale, a.shift, a.clampw, a.decoded, sga);
         return hipGetLastError();
     }
-    if (a.uniforms)
-        hipLaunchKernelGGL((latent_decode_levels_bwd_kernel<LD, F, true>), grid, dim3(kThreads), 0, s, lr, a.latent,
-                           a.div, a.matrix, a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials, sga);
-    else
-        hipLaunchKernelGGL((latent_decode_levels_bwd_kernel<LD, F, false>), grid, dim3(kThreads), 0, s, lr, a.latent,
-                           a.div, a.matrix, a.colscale, a.shift, a.clampw, a.grad_decoded, a.grad_latent, a.partials, sga);
+    if (a.uniforms) decode_bwd_launch<LD, F, true>(grid, plain, lr, a, sga, s);
+    else decode_bwd_launch<LD, F, false>(grid, plain, lr, a, sga, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(finish_level_partials_kernel, dim3(LD * F + 2 * F, levels), dim3(256), 0, s, a.partials, blocks,
-                       LD * F + 2 * F, a.grad_matrix, LD * F, a.grad_colscale, F, a.grad_shift, F);
+    hipLaunchKernelGGL(finish_partials_kernel, dim3(LD * F + 2 * F, levels), dim3(256), 0, s, a.partials, blocks,
+                       LD * F + 2 * F, (const float *)nullptr, a.grad_matrix, LD * F, a.grad_colscale, F, a.grad_shift,
+                       F);
     return hipGetLastError();
 }
-
-typedef hipError_t (*decode_levels_fn)(bool, int, const int64_t *, const DecodeArgs &, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------------------
 // MultiLatentDecoder (reference wisp/models/latent_decoders/multi_latent_decoder.py:27-210, no hidden layers): K affine
@@ -379,15 +301,6 @@ typedef hipError_t (*decode_levels_fn)(bool, int, const int64_t *, const DecodeA
 // One pass each way; the reference evaluates ~20 ATen kernels over [K, T, F] temporaries. Backward: grad_latent, grad_alpha
 // [K, T] (through the softmax), grad_scale [K, S, F], grad_shift [K, F] (fp64 block partials, S = LD for 'sq', 1 for 'dft').
 constexpr int kMultiMaxK = 8;
-
-struct MultiArgs {
-    const float *latent, *alpha, *div, *scale, *dft, *shift, *uniforms, *grad_decoded;
-    float *decoded, *grad_latent, *grad_alpha, *grad_scale, *grad_shift;
-    double *partials;
-    int64_t rows;
-    int K, straight_through, diff_sampling;
-    float temperature, clampw;
-};
 
 template <int LD, int F, bool DFT, bool SGA, bool BWD>
 __global__ __launch_bounds__(kThreads) void multi_decode_kernel(MultiArgs a) {
@@ -592,22 +505,11 @@ static multi_fn multi_lookup(int ld, int f, bool dft) {
 
 bool latent_multi_supported(int ld, int f, int K) { return K >= 1 && K <= kMultiMaxK && multi_lookup(ld, f, false) != nullptr; }
 
-hipError_t latent_multi_dispatch(bool bwd, int ld, int f, bool dft, const float *latent, const float *alpha, int K,
-                                 const float *uniforms, float temperature, int straight_through, int diff_sampling,
-                                 const float *div, const float *scale, const float *dftm, const float *shift,
-                                 float clampw, int64_t rows, float *decoded, const float *grad_decoded,
-                                 float *grad_latent, float *grad_alpha, float *grad_scale, float *grad_shift,
-                                 double *partials, hipStream_t s) {
-    MultiArgs a{};
-    a.latent = latent; a.alpha = alpha; a.div = div; a.scale = scale; a.dft = dftm; a.shift = shift;
-    a.uniforms = uniforms; a.grad_decoded = grad_decoded; a.decoded = decoded; a.grad_latent = grad_latent;
-    a.grad_alpha = grad_alpha; a.grad_scale = grad_scale; a.grad_shift = grad_shift; a.partials = partials;
-    a.rows = rows; a.K = K; a.straight_through = straight_through; a.diff_sampling = diff_sampling;
-    a.temperature = temperature; a.clampw = clampw;
+hipError_t latent_multi_dispatch(bool bwd, int ld, int f, bool dft, const MultiArgs &a, hipStream_t s) {
     return multi_lookup(ld, f, dft)(bwd, a, s);
 }
 
-typedef hipError_t (*decode_fn)(bool, const DecodeArgs &, hipStream_t);
+typedef hipError_t (*decode_fn)(bool, int, const int64_t *, const DecodeArgs &, hipStream_t);
 
 static decode_fn decode_lookup(int ld, int f) {
 #define SHACIRA_DEC(LD, F) \
@@ -621,27 +523,11 @@ static decode_fn decode_lookup(int ld, int f) {
     return nullptr;
 }
 
-static decode_levels_fn decode_levels_lookup(int ld, int f) {
-#define SHACIRA_DECL(LD, F) \
-    if (ld == LD && f == F) return &decode_levels_launch<LD, F>;
-    SHACIRA_DECL(1, 1) SHACIRA_DECL(1, 2) SHACIRA_DECL(1, 4) SHACIRA_DECL(1, 8)
-    SHACIRA_DECL(2, 1) SHACIRA_DECL(2, 2) SHACIRA_DECL(2, 4) SHACIRA_DECL(2, 8)
-    SHACIRA_DECL(3, 1) SHACIRA_DECL(3, 2) SHACIRA_DECL(3, 4) SHACIRA_DECL(3, 8)
-    SHACIRA_DECL(4, 1) SHACIRA_DECL(4, 2) SHACIRA_DECL(4, 4) SHACIRA_DECL(4, 8)
-    SHACIRA_DECL(8, 2) SHACIRA_DECL(8, 4) SHACIRA_DECL(8, 8)
-#undef SHACIRA_DECL
-    return nullptr;
-}
-
-hipError_t latent_decode_levels_dispatch(bool bwd, int ld, int f, int levels, const int64_t *offsets,
-                                         const DecodeArgs &a, hipStream_t s) {
-    return decode_levels_lookup(ld, f)(bwd, levels, offsets, a, s);
-}
-
 bool latent_decode_supported(int ld, int f) { return decode_lookup(ld, f) != nullptr; }
 
-hipError_t latent_decode_dispatch(bool bwd, int ld, int f, const DecodeArgs &a, hipStream_t s) {
-    return decode_lookup(ld, f)(bwd, a, s);
+hipError_t latent_decode_dispatch(bool bwd, int ld, int f, int levels, const int64_t *offsets, const DecodeArgs &a,
+                                  hipStream_t s) {
+    return decode_lookup(ld, f)(bwd, levels, offsets, a, s);
 }
 
 // =========================================================================================================
@@ -687,14 +573,14 @@ __device__ __forceinline__ float tanhf_fast(float u) {
 }
 
 // CDF with the chain's intermediates kept for the backward (NL = num_layers; layers used: first NL-1 of f1..f3, then f4)
-template <int LD> struct CdfTrace {
+struct CdfTrace {
     float xin[4];  // input of each applied layer (index = layer slot 0..2, 3 = final)
     float th[3];   // tanh(u) of each applied non-final layer
     float s;       // sigmoid output
 };
 
 template <int LD, int NL>
-__device__ __forceinline__ float cdf_eval(const CdfConsts<LD> &p, int c, float x, CdfTrace<LD> &tr) {
+__device__ __forceinline__ float cdf_eval(const CdfConsts<LD> &p, int c, float x, CdfTrace &tr) {
     constexpr int nl = NL;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -713,8 +599,8 @@ __device__ __forceinline__ float cdf_eval(const CdfConsts<LD> &p, int c, float x
 
 // back-propagates g = dL/d(cdf output); accumulates parameter grads into acc[(k*3+slot)*LD + c]; returns dL/dx
 template <int LD, int NL>
-__device__ __forceinline__ float cdf_backward(const CdfConsts<LD> &p, const float *__restrict__ prm, int c,
-                                              const CdfTrace<LD> &tr, float g, float (&acc)[12 * LD]) {
+__device__ __forceinline__ float cdf_backward(const CdfConsts<LD> &p, int c, const CdfTrace &tr, float g,
+                                              float (&acc)[12 * LD]) {
     constexpr int nl = NL;
     float du = g * tr.s * (1.0f - tr.s);
     acc[(3 * 3 + 0) * LD + c] += du * tr.xin[3] * p.sgh[3][c];
@@ -732,7 +618,6 @@ __device__ __forceinline__ float cdf_backward(const CdfConsts<LD> &p, const floa
             dx = du * p.sp[k][c];
         }
     }
-    (void)prm;
     return dx;
 }
 
@@ -752,7 +637,7 @@ __global__ __launch_bounds__(kThreads) void entropy_fwd_kernel(const float *__re
         for (int c = 0; c < LD; ++c) {
             const float v = latent[r * LD + c];
             const float w = noise ? (v + noise[r * LD + c]) : rintf(v);
-            CdfTrace<LD> tp, tn;
+            CdfTrace tp, tn;
             const float prob = cdf_eval<LD, NL>(p, c, w + 0.5f, tp) - cdf_eval<LD, NL>(p, c, w - 0.5f, tn);
             float bits = -__log2f(prob + 1e-10f);      // hardware log2, 1 ulp
             bits = bits < 0.0f ? 0.0f : (bits > 50.0f ? 50.0f : bits);   // torch.clamp: a NaN stays a NaN
@@ -781,14 +666,14 @@ __global__ __launch_bounds__(kThreads) void entropy_bwd_kernel(const float *__re
         for (int c = 0; c < LD; ++c) {
             const float v = latent[r * LD + c];
             const float w = noise ? (v + noise[r * LD + c]) : rintf(v);
-            CdfTrace<LD> tp, tn;
+            CdfTrace tp, tn;
             const float prob = cdf_eval<LD, NL>(p, c, w + 0.5f, tp) - cdf_eval<LD, NL>(p, c, w - 0.5f, tn);
             const float q = prob + 1e-10f;
             const float bits = -__log2f(q);
             // clamp(., 0, 50) passes the gradient on the closed interval; parameter grads are scaled by gt at the end
             const float gp = (bits >= 0.0f && bits <= 50.0f) ? -kInvLn2 * __frcp_rn(q) : 0.0f;
-            const float dxp = cdf_backward<LD, NL>(p, prm, c, tp, gp, acc);
-            const float dxn = cdf_backward<LD, NL>(p, prm, c, tn, -gp, acc);
+            const float dxp = cdf_backward<LD, NL>(p, c, tp, gp, acc);
+            const float dxn = cdf_backward<LD, NL>(p, c, tn, -gp, acc);
             if (grad_latent) grad_latent[r * LD + c] = noise ? gt * (dxp + dxn) : 0.0f;  // round(): zero gradient
         }
     }

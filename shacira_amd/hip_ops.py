@@ -446,90 +446,104 @@ def _latent_workspace(device):
     return torch.empty((n,), dtype=torch.uint8, device=device)
 
 
-def latent_decode_forward(latent, div, matrix, colscale, shift, clamp_weights):
-    _need_gpu(latent, div, matrix, colscale, shift)
-    T, ld = latent.shape
-    F = matrix.shape[1]
-    out = torch.empty((T, F), dtype=torch.float32, device=latent.device)
-    with _on_device(latent.device):
-        rc = _lib.lib().shacira_latent_decode_forward(T, ld, F, _ptr(latent), _ptr(div), _ptr(matrix), _ptr(colscale),
-                                                      _ptr(shift), float(clamp_weights), _ptr(out), _stream(latent))
-    _lib.check(rc, "latent_decode_forward")
-    return out
-
-
-def latent_decode_backward(latent, div, matrix, colscale, shift, clamp_weights, grad_decoded, need_colscale):
-    _need_gpu(latent, grad_decoded)
-    T, ld = latent.shape
-    F = matrix.shape[1]
-    dev = latent.device
-    g_lat = torch.empty_like(latent)
-    g_mat = torch.empty((ld, F), dtype=torch.float32, device=dev)
-    g_cs = torch.empty((F,), dtype=torch.float32, device=dev) if need_colscale else None
-    g_sh = torch.empty((F,), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        ws = _latent_workspace(dev)
-        rc = _lib.lib().shacira_latent_decode_backward(T, ld, F, _ptr(latent), _ptr(div), _ptr(matrix), _ptr(colscale),
-                                                       _ptr(shift), float(clamp_weights), _ptr(grad_decoded),
-                                                       _ptr(g_lat), _ptr(g_mat), _ptr(g_cs), _ptr(g_sh), _ptr(ws),
-                                                       ws.numel(), _stream(latent))
-    _lib.check(rc, "latent_decode_backward")
-    return g_lat, g_mat, g_cs, g_sh
-
-
-def latent_decode_sga_forward(latent, uniforms, temperature, diff_sampling, div, matrix, colscale, shift, clamp_weights):
-    """SGA sample (reference basic_latent_decoder.py:183-191) + decode in one kernel; ``uniforms`` [T, ld, 2]."""
-    _need_gpu(latent, uniforms, div, matrix, colscale, shift)
-    T, ld = latent.shape
-    F = matrix.shape[1]
-    if tuple(uniforms.shape) != (T, ld, 2) or uniforms.dtype != torch.float32 or not uniforms.is_contiguous():
-        raise RuntimeError("uniforms must be a contiguous fp32 [rows, latent_dim, 2] tensor")
-    out = torch.empty((T, F), dtype=torch.float32, device=latent.device)
-    with _on_device(latent.device):
-        if torch.is_tensor(temperature):     # one fp32 value in device memory (graph-captured steps anneal it between replays)
-            _check_device_scalar(temperature, latent.device)
-            rc = _lib.lib().shacira_latent_decode_sga_forward_tdev(
-                T, ld, F, _ptr(latent), _ptr(uniforms), _ptr(temperature), int(bool(diff_sampling)), _ptr(div), _ptr(matrix),
-                _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(out), _stream(latent))
-        else:
-            rc = _lib.lib().shacira_latent_decode_sga_forward(T, ld, F, _ptr(latent), _ptr(uniforms), float(temperature),
-                                                              int(bool(diff_sampling)), _ptr(div), _ptr(matrix),
-                                                              _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(out),
-                                                              _stream(latent))
-    _lib.check(rc, "latent_decode_sga_forward")
-    return out
-
-
 def _check_device_scalar(t, device):
     if t.device != device or t.dtype != torch.float32 or t.numel() != 1:
         raise RuntimeError("a device-side temperature must be one fp32 value on the table's device")
 
 
-def latent_decode_sga_backward(latent, uniforms, temperature, diff_sampling, div, matrix, colscale, shift, clamp_weights,
-                               grad_decoded, need_colscale):
-    _need_gpu(latent, uniforms, grad_decoded)
+def _offsets_array(offsets):
+    return (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
+
+
+def _decode_entry(name, latent, F, offsets, sga):
+    """-> (the C entry point ``shacira_<name>``, its arguments ahead of ``div``). ``offsets`` (host ints, [L+1]) selects the
+    per-level ABI; ``sga`` is None (plain ABI) or (uniforms, temperature, diff_sampling). Without ``offsets`` the temperature
+    may be one fp32 value in device memory (graph-captured steps anneal it between replays): the ``_tdev`` entry point."""
     T, ld = latent.shape
-    F = matrix.shape[1]
+    args = (T, ld, F, _ptr(latent))
+    if offsets is not None:
+        args = (len(offsets) - 1, _offsets_array(offsets)) + args
+    if sga is not None:
+        uniforms, temperature, diff_sampling = sga
+        if offsets is None and torch.is_tensor(temperature):
+            _check_device_scalar(temperature, latent.device)
+            name, temperature = name + "_tdev", _ptr(temperature)
+        else:
+            temperature = float(temperature)
+        args += (_ptr(uniforms), temperature, int(bool(diff_sampling)))
+    return getattr(_lib.lib(), "shacira_" + name), args
+
+
+def _decode_forward(name, latent, offsets, sga, div, matrix, colscale, shift, clamp_weights):
+    uniforms = sga[0] if sga is not None else None
+    _need_gpu(latent, uniforms, div, matrix, colscale, shift)
+    T, ld = latent.shape
+    F = matrix.shape[-1]
+    if offsets is None and sga is not None and (tuple(uniforms.shape) != (T, ld, 2) or uniforms.dtype != torch.float32
+                                                or not uniforms.is_contiguous()):
+        raise RuntimeError("uniforms must be a contiguous fp32 [rows, latent_dim, 2] tensor")
+    out = torch.empty((T, F), dtype=torch.float32, device=latent.device)
+    with _on_device(latent.device):
+        fn, args = _decode_entry(name, latent, F, offsets, sga)
+        rc = fn(*args, _ptr(div), _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(out),
+                _stream(latent))
+    _lib.check(rc, name)
+    return out
+
+
+def _decode_backward(name, latent, offsets, sga, div, matrix, colscale, shift, clamp_weights, grad_decoded, need_colscale):
+    """-> grad_latent [T, ld], grad_matrix [ld, F], grad_colscale [F] or None, grad_shift [F]; per level ([L, ...]) with
+    ``offsets``."""
+    _need_gpu(latent, sga[0] if sga is not None else None, grad_decoded)
+    ld, F = latent.shape[1], matrix.shape[-1]
+    lead = () if offsets is None else (len(offsets) - 1,)
     dev = latent.device
     g_lat = torch.empty_like(latent)
-    g_mat = torch.empty((ld, F), dtype=torch.float32, device=dev)
-    g_cs = torch.empty((F,), dtype=torch.float32, device=dev) if need_colscale else None
-    g_sh = torch.empty((F,), dtype=torch.float32, device=dev)
+    g_mat = torch.empty(lead + (ld, F), dtype=torch.float32, device=dev)
+    g_cs = torch.empty(lead + (F,), dtype=torch.float32, device=dev) if need_colscale else None
+    g_sh = torch.empty(lead + (F,), dtype=torch.float32, device=dev)
     with _on_device(dev):
         ws = _latent_workspace(dev)
-        if torch.is_tensor(temperature):
-            _check_device_scalar(temperature, dev)
-            rc = _lib.lib().shacira_latent_decode_sga_backward_tdev(
-                T, ld, F, _ptr(latent), _ptr(uniforms), _ptr(temperature), int(bool(diff_sampling)), _ptr(div),
-                _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(grad_decoded), _ptr(g_lat),
-                _ptr(g_mat), _ptr(g_cs), _ptr(g_sh), _ptr(ws), ws.numel(), _stream(latent))
-        else:
-            rc = _lib.lib().shacira_latent_decode_sga_backward(
-                T, ld, F, _ptr(latent), _ptr(uniforms), float(temperature), int(bool(diff_sampling)), _ptr(div),
-                _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(grad_decoded), _ptr(g_lat),
-                _ptr(g_mat), _ptr(g_cs), _ptr(g_sh), _ptr(ws), ws.numel(), _stream(latent))
-    _lib.check(rc, "latent_decode_sga_backward")
+        fn, args = _decode_entry(name, latent, F, offsets, sga)
+        rc = fn(*args, _ptr(div), _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights), _ptr(grad_decoded),
+                _ptr(g_lat), _ptr(g_mat), _ptr(g_cs), _ptr(g_sh), _ptr(ws), ws.numel(), _stream(latent))
+    _lib.check(rc, name)
     return g_lat, g_mat, g_cs, g_sh
+
+
+def latent_decode_forward(latent, div, matrix, colscale, shift, clamp_weights):
+    return _decode_forward("latent_decode_forward", latent, None, None, div, matrix, colscale, shift, clamp_weights)
+
+
+def latent_decode_backward(latent, div, matrix, colscale, shift, clamp_weights, grad_decoded, need_colscale):
+    return _decode_backward("latent_decode_backward", latent, None, None, div, matrix, colscale, shift, clamp_weights,
+                            grad_decoded, need_colscale)
+
+
+def latent_decode_sga_forward(latent, uniforms, temperature, diff_sampling, div, matrix, colscale, shift, clamp_weights):
+    """SGA sample (reference basic_latent_decoder.py:183-191) + decode in one kernel; ``uniforms`` [T, ld, 2]."""
+    return _decode_forward("latent_decode_sga_forward", latent, None, (uniforms, temperature, diff_sampling), div, matrix,
+                           colscale, shift, clamp_weights)
+
+
+def latent_decode_sga_backward(latent, uniforms, temperature, diff_sampling, div, matrix, colscale, shift, clamp_weights,
+                               grad_decoded, need_colscale):
+    return _decode_backward("latent_decode_sga_backward", latent, None, (uniforms, temperature, diff_sampling), div, matrix,
+                            colscale, shift, clamp_weights, grad_decoded, need_colscale)
+
+
+def latent_decode_levels_forward(latent, offsets, uniforms, temperature, diff_sampling, div, matrix, colscale, shift,
+                                 clamp_weights):
+    """Per-level decoders in one launch: ``offsets`` (host ints, [L+1]) bound the levels' rows; ``div`` [L, ld],
+    ``matrix`` [L, ld, F], ``colscale`` / ``shift`` [L, F] or None; ``uniforms`` [T, ld, 2] selects the SGA path."""
+    return _decode_forward("latent_decode_levels_forward", latent, offsets, (uniforms, temperature, diff_sampling), div,
+                           matrix, colscale, shift, clamp_weights)
+
+
+def latent_decode_levels_backward(latent, offsets, uniforms, temperature, diff_sampling, div, matrix, colscale, shift,
+                                  clamp_weights, grad_decoded):
+    return _decode_backward("latent_decode_levels_backward", latent, offsets, (uniforms, temperature, diff_sampling), div,
+                            matrix, colscale, shift, clamp_weights, grad_decoded, colscale is not None)
 
 
 LATENT_ACTIVATIONS = {"none": 0, "sigmoid": 1, "tanh": 2, "relu": 3, "sine": 4}   # SHACIRA_ACT_*
@@ -598,47 +612,6 @@ def latent_mlp_backward(latent, uniforms, temperature, diff_sampling, div, param
             _ptr(grad_decoded), _ptr(g_lat), _ptr(g_par), _ptr(ws), ws.numel(), _stream(latent))
     _lib.check(rc, "latent_mlp_backward")
     return g_lat, g_par
-
-
-def _offsets_array(offsets):
-    return (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
-
-
-def latent_decode_levels_forward(latent, offsets, uniforms, temperature, diff_sampling, div, matrix, colscale, shift,
-                                 clamp_weights):
-    """Per-level decoders in one launch: ``offsets`` (host ints, [L+1]) bound the levels' rows; ``div`` [L, ld],
-    ``matrix`` [L, ld, F], ``colscale`` / ``shift`` [L, F] or None; ``uniforms`` [T, ld, 2] selects the SGA path."""
-    _need_gpu(latent, uniforms, div, matrix, colscale, shift)
-    T, ld = latent.shape
-    F = matrix.shape[-1]
-    out = torch.empty((T, F), dtype=torch.float32, device=latent.device)
-    with _on_device(latent.device):
-        rc = _lib.lib().shacira_latent_decode_levels_forward(
-            len(offsets) - 1, _offsets_array(offsets), T, ld, F, _ptr(latent), _ptr(uniforms), float(temperature),
-            int(bool(diff_sampling)), _ptr(div), _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights),
-            _ptr(out), _stream(latent))
-    _lib.check(rc, "latent_decode_levels_forward")
-    return out
-
-
-def latent_decode_levels_backward(latent, offsets, uniforms, temperature, diff_sampling, div, matrix, colscale, shift,
-                                  clamp_weights, grad_decoded):
-    _need_gpu(latent, grad_decoded)
-    T, ld = latent.shape
-    L, F = len(offsets) - 1, matrix.shape[-1]
-    dev = latent.device
-    g_lat = torch.empty_like(latent)
-    g_mat = torch.empty((L, ld, F), dtype=torch.float32, device=dev)
-    g_cs = torch.empty((L, F), dtype=torch.float32, device=dev) if colscale is not None else None
-    g_sh = torch.empty((L, F), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        ws = _latent_workspace(dev)
-        rc = _lib.lib().shacira_latent_decode_levels_backward(
-            L, _offsets_array(offsets), T, ld, F, _ptr(latent), _ptr(uniforms), float(temperature),
-            int(bool(diff_sampling)), _ptr(div), _ptr(matrix), _ptr(colscale), _ptr(shift), float(clamp_weights),
-            _ptr(grad_decoded), _ptr(g_lat), _ptr(g_mat), _ptr(g_cs), _ptr(g_sh), _ptr(ws), ws.numel(), _stream(latent))
-    _lib.check(rc, "latent_decode_levels_backward")
-    return g_lat, g_mat, g_cs, g_sh
 
 
 def latent_multi_supported(latent_dim, feature_dim, num_decoders):

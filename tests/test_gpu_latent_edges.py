@@ -342,7 +342,7 @@ LEVEL_LENGTHS = [0, 1, 255, 256, 257, 32_768, 32_769] + [301 + 7 * i for i in ra
 
 @pytest.mark.parametrize("sga", [None, True])
 def test_per_level_decoders_at_their_grid_cap(dev, sga):
-    """latent_decode_levels_*: 16 levels of 0, 1, 255, 256, 257, 32 768 and 32 769 rows (decode_levels_launch caps the grid at
+    """latent_decode_levels_*: 16 levels of 0, 1, 255, 256, 257, 32 768 and 32 769 rows (decode_launch caps the grid at
     2048 / 16 = 128 workgroups per level: 32 768 rows fill it, 32 769 make one thread take a second row), nine more of 301..357
     rows, and 33 rows no level owns. Each level's slice against the float64 reference of that slice with that level's
     parameters; the unowned tail is exactly zero each way."""
@@ -371,6 +371,36 @@ def test_per_level_decoders_at_their_grid_cap(dev, sga):
     assert _rows_per_thread(32_769, 2048 // L) == 2 and _rows_per_thread(32_768, 2048 // L) == 1
     assert not out[offsets[-1]:].any() and not gl[offsets[-1]:].any()              # exact zeros, no NaN
     assert not gm[0].any() and not gc[0].any() and not gsh[0].any()                 # the empty level's gradients
+
+
+@pytest.mark.parametrize("rows", [1, 257, BIG])
+@pytest.mark.parametrize("ld,F", [(1, 1), (2, 2), (8, 8)])
+def test_one_level_is_the_plain_decoder(dev, ld, F, rows):
+    """The contract the shared row loops rest on (the plain backward enters them through a kernel entry of its own, the
+    per-level one through LevelRows): latent_decode_levels_* with the one level [0, T] and parameters stacked
+    to [1, ...] give, bit for bit, what latent_decode_* give, and with uniforms what latent_decode_sga_* give with the
+    temperature on the host and in device memory. 1 row is a single lane, 257 one row past a workgroup, 524 545 above the
+    grid cap (a thread takes two rows, the finish loop makes several trips)."""
+    ops = _ops()
+    p = _decode_inputs(ld * 10 + F, rows, ld, F)
+    lat, go = _to(dev, p["latent"]), _to(dev, p["grad_out"])
+    par = tuple(_to(dev, p[k]) for k in ("div", "matrix", "colscale", "shift"))
+    stacked = tuple(x.unsqueeze(0).contiguous() for x in par)
+    uni = _to(dev, p["rng"].random((rows, ld, 2), dtype=np.float32))
+
+    def levels(u):
+        a = (lat, [0, rows], u, 0.7, True, *stacked, 0.0)
+        return (ops.latent_decode_levels_forward(*a),) + tuple(ops.latent_decode_levels_backward(*a, go))
+
+    def sga(temperature):
+        return (ops.latent_decode_sga_forward(lat, uni, temperature, True, *par, 0.0),) + tuple(
+            ops.latent_decode_sga_backward(lat, uni, temperature, True, *par, 0.0, go, True))
+
+    plain = (ops.latent_decode_forward(lat, *par, 0.0),) + tuple(ops.latent_decode_backward(lat, *par, 0.0, go, True))
+    on_device = torch.full((1,), 0.7, dtype=torch.float32, device=dev)
+    for tag, got, want in (("plain", levels(None), plain), ("sga", levels(uni), sga(0.7)), ("device T", levels(uni), sga(on_device))):
+        for name, g, w in zip(("decoded", "grad_latent", "grad_matrix", "grad_colscale", "grad_shift"), got, want):
+            assert g.numel() == w.numel() and torch.equal(g.reshape(w.shape), w), f"{tag}: {name} differs"
 
 
 @pytest.mark.parametrize("temperature", [1.0, 0.05])
