@@ -626,6 +626,57 @@ SHACIRA_API int shacira_ssim_backward(int64_t height, int64_t width, int pixel_s
                                       size_t workspace_bytes, void *stream);
 
 /*
+ * Positional-encoding rows: the decoder MLP's input [prefix | coords | sin | cos] written by one kernel, what
+ * torch.cat([prefix, PositionalEmbedder(coords)], -1) builds from seven (wisp/models/embedders/positional_embedder.py:60-66,
+ * wisp/models/nefs/image.py:146-148). All operands fp32; every stride counts floats between the starts of two rows.
+ *   n              rows; 0 returns 0 with nothing enqueued, whatever the pointers and strides (d, num_bands and prefix_width
+ *                  are checked first)
+ *   d              coordinates per row, 1 .. SHACIRA_POSENC_MAX_DIM
+ *   num_bands      F, 1 .. SHACIRA_POSENC_MAX_BANDS; bands[F] on the device, any values (linear sampling gives non-powers of two)
+ *   include_input  non-zero: the coordinates are part of the row, I = d; zero: I = 0
+ *   prefix_width   P, 0 .. SHACIRA_POSENC_MAX_PREFIX; prefix [n, P] may be NULL when P == 0
+ *   E = I + 2 d F, the row is P + E wide:
+ *     col 0 .. P-1              prefix, copied bit for bit
+ *     col P .. P+I-1            coords, copied bit for bit (-0.0, Inf and NaN payloads included)
+ *     col P+I + k*d + j         sin(a_kj)       a_kj = coords[j] * bands[k], ONE fp32 multiply
+ *     col P+I + d*F + k*d + j   cos(a_kj)       both from the device library's sincosf (full-range reduction; a non-finite
+ *                                               a_kj gives NaN in both columns)
+ *   out            [n, >= P+E] with out_stride >= P+E; columns beyond P+E are not written
+ * shacira_posenc_backward: the gradient with respect to the coordinates from the SAVED row of the forward (`row`, any
+ * row_stride >= P+E; only its sin / cos columns are read) and grad_out (same layout, own stride); no trigonometry, the
+ * coordinates are not needed. grad_coords [n, d] dense, overwritten:
+ *     gc_j = [I > 0] g_in_j + sum_k bands[k] * (cos_kj * g_sin_kj - sin_kj * g_cos_kj)
+ * fp32, one rounding per operator, the terms added in k order onto g_in_j (onto 0 without it). The gradient with respect to
+ * the prefix is grad_out[:, :P] itself: no kernel.
+ * shacira_posenc_backward2: the backward of that call. With gg [n, d] dense = dL/d(grad_coords) it overwrites two dense
+ * [n, P+E] arrays:
+ *     grad_row        sin col: -(b_k g_cos_kj) gg_j     cos col: +(b_k g_sin_kj) gg_j     every other column: 0
+ *     grad_grad_out   sin col: +(b_k cos_kj) gg_j       cos col: -(b_k sin_kj) gg_j       input col j: gg_j     prefix: 0
+ * grad_row is a gradient with respect to the forward's OUTPUT: sent through shacira_posenc_backward once more it yields the
+ * -sum_k b_k^2 (...) term of the second derivative with respect to the coordinates.
+ *
+ * Pointers need the 4-byte alignment of a float only; when P is a multiple of 4 and prefix, out and their strides are multiples
+ * of 16 bytes the prefix moves 16 bytes at a time, with the same result. Validation precedes any HIP call: n < 0, d, num_bands
+ * or prefix_width out of range, a NULL operand (prefix only when P > 0), out_stride / row_stride / grad_stride < P+E,
+ * coords_stride < d, prefix_stride < P, or n * stride beyond 2^59 return SHACIRA_EINVAL and nothing is enqueued. No workspace,
+ * no allocation, no synchronisation, no atomics: everything runs on `stream`, is capturable, and two calls on the same operands
+ * return the same bits.
+ */
+#define SHACIRA_POSENC_MAX_DIM 4
+#define SHACIRA_POSENC_MAX_BANDS 64
+#define SHACIRA_POSENC_MAX_PREFIX (1 << 30)
+SHACIRA_API int shacira_posenc_forward(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width,
+                                       const float *coords, int64_t coords_stride, const float *prefix, int64_t prefix_stride,
+                                       const float *bands, float *out, int64_t out_stride, void *stream);
+SHACIRA_API int shacira_posenc_backward(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width,
+                                        const float *row, int64_t row_stride, const float *grad_out, int64_t grad_stride,
+                                        const float *bands, float *grad_coords, void *stream);
+SHACIRA_API int shacira_posenc_backward2(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width,
+                                         const float *gg, const float *row, int64_t row_stride, const float *grad_out,
+                                         int64_t grad_stride, const float *bands, float *grad_row, float *grad_grad_out,
+                                         void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

@@ -22,6 +22,7 @@ MESH_CLOSEST_SIGNED = 1
 MESH_VOXELIZE_PASS_TRIANGLES = 32768                          # SHACIRA_MESH_VOXELIZE_PASS_TRIANGLES
 OCTREE_MAX_LEVEL = 10                                         # SHACIRA_OCTREE_MAX_LEVEL
 SSIM_WINDOW, SSIM_TILE_H, SSIM_TILE_W = 11, 16, 64            # SHACIRA_SSIM_* of the header
+POSENC_MAX_DIM, POSENC_MAX_BANDS, POSENC_MAX_PREFIX = 4, 64, 1 << 30   # SHACIRA_POSENC_* of the header
 
 _lock = threading.Lock()
 _lib = None
@@ -69,7 +70,10 @@ SIGNATURES = {
     "shacira_ssim_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
     "shacira_ssim_forward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),
     "shacira_ssim_backward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),
-    "shacira_find_depth_bound": (_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "shacira_posenc_forward": (_i, [_i64, _i, _i, _i, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "shacira_posenc_backward": (_i, [_i64, _i, _i, _i, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
+    "shacira_posenc_backward2": (_i, [_i64, _i, _i, _i, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "shacira_find_depth_bound":(_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),
     "shacira_latent_decode_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),

@@ -599,6 +599,66 @@ int shacira_ssim_backward(int64_t height, int64_t width, int pixel_stride, int c
                                        (hipStream_t)stream);
 }
 
+// ---- positional-encoding rows ----------------------------------------------------------------------------------------------
+// the shape shared by the three calls; `width` = P + E. Row strides are checked by the callers
+static bool posenc_shape_ok(int64_t n, int d, int num_bands, int64_t prefix_width, int64_t *width) {
+    if (n < 0 || prefix_width < 0 || prefix_width > SHACIRA_POSENC_MAX_PREFIX) return false;
+    if (d < 1 || d > SHACIRA_POSENC_MAX_DIM || num_bands < 1 || num_bands > SHACIRA_POSENC_MAX_BANDS) return false;
+    *width = prefix_width + 2 * (int64_t)d * num_bands;
+    return true;
+}
+
+static bool posenc_rows_fit(int64_t n, int64_t stride) {       // byte offsets stay inside int64
+    return stride <= INT64_MAX / 16 / (n > 0 ? n : 1);
+}
+
+int shacira_posenc_forward(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width, const float *coords,
+                           int64_t coords_stride, const float *prefix, int64_t prefix_stride, const float *bands, float *out,
+                           int64_t out_stride, void *stream) {
+    int64_t width;
+    if (!posenc_shape_ok(n, d, num_bands, prefix_width, &width)) return SHACIRA_EINVAL;
+    const int I = include_input ? d : 0;
+    width += I;
+    if (n == 0) return 0;                       // an empty batch may come with NULL operands
+    if (!coords || !bands || !out || (prefix_width > 0 && !prefix)) return SHACIRA_EINVAL;
+    if (out_stride < width || coords_stride < d || (prefix_width > 0 && prefix_stride < prefix_width)) return SHACIRA_EINVAL;
+    if (!posenc_rows_fit(n, out_stride) || !posenc_rows_fit(n, coords_stride) ||
+        (prefix_width > 0 && !posenc_rows_fit(n, prefix_stride)))
+        return SHACIRA_EINVAL;
+    return (int)posenc_forward_dispatch(n, d, num_bands, I, (int)prefix_width, coords, coords_stride, prefix,
+                                        prefix_width > 0 ? prefix_stride : 0, bands, out, out_stride, (hipStream_t)stream);
+}
+
+int shacira_posenc_backward(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width, const float *row,
+                            int64_t row_stride, const float *grad_out, int64_t grad_stride, const float *bands,
+                            float *grad_coords, void *stream) {
+    int64_t width;
+    if (!posenc_shape_ok(n, d, num_bands, prefix_width, &width)) return SHACIRA_EINVAL;
+    const int I = include_input ? d : 0;
+    width += I;
+    if (n == 0) return 0;
+    if (!row || !grad_out || !bands || !grad_coords) return SHACIRA_EINVAL;
+    if (row_stride < width || grad_stride < width) return SHACIRA_EINVAL;
+    if (!posenc_rows_fit(n, row_stride) || !posenc_rows_fit(n, grad_stride)) return SHACIRA_EINVAL;
+    return (int)posenc_backward_dispatch(n, d, num_bands, I, (int)prefix_width, row, row_stride, grad_out, grad_stride, bands,
+                                         grad_coords, (hipStream_t)stream);
+}
+
+int shacira_posenc_backward2(int64_t n, int d, int num_bands, int include_input, int64_t prefix_width, const float *gg,
+                             const float *row, int64_t row_stride, const float *grad_out, int64_t grad_stride,
+                             const float *bands, float *grad_row, float *grad_grad_out, void *stream) {
+    int64_t width;
+    if (!posenc_shape_ok(n, d, num_bands, prefix_width, &width)) return SHACIRA_EINVAL;
+    const int I = include_input ? d : 0;
+    width += I;
+    if (n == 0) return 0;
+    if (!gg || !row || !grad_out || !bands || !grad_row || !grad_grad_out) return SHACIRA_EINVAL;
+    if (row_stride < width || grad_stride < width) return SHACIRA_EINVAL;
+    if (!posenc_rows_fit(n, row_stride) || !posenc_rows_fit(n, grad_stride)) return SHACIRA_EINVAL;
+    return (int)posenc_backward2_dispatch(n, d, num_bands, I, (int)prefix_width, gg, row, row_stride, grad_out, grad_stride,
+                                          bands, grad_row, grad_grad_out, (hipStream_t)stream);
+}
+
 // ---- sphere tracing over ray packs ---------------------------------------------------------------------------------------
 static bool trace_counts_ok(int64_t num_packs, int64_t num_nugs) {
     return num_packs >= 0 && num_nugs >= 0 && num_packs <= INT32_MAX && num_nugs <= INT32_MAX && num_packs <= num_nugs;

@@ -161,6 +161,18 @@ hipError_t ssim_forward_dispatch(int64_t H, int64_t W, int cin, int C, const flo
 hipError_t ssim_backward_dispatch(int64_t H, int64_t W, int cin, int C, const float *x, const float *y, float data_range,
                                   const float *grad, float *grad_x, void *workspace, hipStream_t s);
 
+// posenc.hip: the decoder's input row [prefix | coords | sin | cos] and its two backward passes (arguments checked by the entry
+// points; I = d when the coordinates are part of the row, else 0; strides in floats)
+hipError_t posenc_forward_dispatch(int64_t n, int d, int F, int I, int P, const float *coords, int64_t cstride,
+                                   const float *prefix, int64_t pstride, const float *bands, float *out, int64_t ostride,
+                                   hipStream_t s);
+hipError_t posenc_backward_dispatch(int64_t n, int d, int F, int I, int P, const float *row, int64_t rstride,
+                                    const float *grad_out, int64_t gstride, const float *bands, float *grad_coords,
+                                    hipStream_t s);
+hipError_t posenc_backward2_dispatch(int64_t n, int d, int F, int I, int P, const float *gg, const float *row, int64_t rstride,
+                                     const float *grad_out, int64_t gstride, const float *bands, float *grad_row,
+                                     float *grad_grad, hipStream_t s);
+
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
                                    const float *depth, int32_t *out, hipStream_t s);

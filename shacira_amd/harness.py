@@ -169,6 +169,8 @@ class ImageFitter:
             if self.iteration / self.total_steps > self.cdec["decay_period"]:
                 dec.use_sga = False
         pred = self.nef.rgb(self.coords)
+        if isinstance(pred, dict):      # wisp.models.nefs.NeuralImage returns its channels by name
+            pred = pred["rgb"]
         # mean over the GLOBAL batch: local sum / global element count (gradients are summed over ranks)
         sq_sum = ((pred - self.rgb) ** 2).sum()
         loss = sq_sum / (self.global_pixels * 3)

@@ -1146,3 +1146,105 @@ def ssim_backward(pred, target, grad, channels=None, data_range=1.0):
                                      _ptr(ws), nbytes, _stream(pred))
     _lib.check(rc, "ssim_backward")
     return grad_pred
+
+
+# ---- positional-encoding rows (include/shacira_hip.h, shacira_posenc_forward / _backward / _backward2) -------------------------
+def _posenc_rows(t, width, what):
+    """``t`` as an fp32 [N, width] device operand of the row kernels and its row stride in floats: a tensor whose last stride is
+    not 1 (or whose rows overlap) is made contiguous, a row-strided view such as ``x[:, :3]`` is passed as it is."""
+    _need_gpu(t)
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"shacira_amd: posenc expects fp32 {what}, got {t.dtype}")
+    if t.dim() != 2 or (width is not None and t.shape[1] != width):
+        raise RuntimeError(f"shacira_amd: posenc expects {what} [N, {width if width is not None else 'd'}], got "
+                           f"{tuple(t.shape)}")
+    t = t.detach()
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1))
+
+
+def _posenc_shape(d, bands, include_input, prefix_width):
+    F = bands.numel()
+    if not 1 <= d <= _lib.POSENC_MAX_DIM or not 1 <= F <= _lib.POSENC_MAX_BANDS or bands.dim() != 1:
+        raise RuntimeError(f"shacira_amd: posenc takes 1..{_lib.POSENC_MAX_DIM} coordinates and 1..{_lib.POSENC_MAX_BANDS} "
+                           f"bands, got d = {d}, bands {tuple(bands.shape)}")
+    if bands.dtype != torch.float32 or not bands.is_cuda:
+        raise RuntimeError("shacira_amd: posenc expects fp32 bands on the device")
+    return F, int(prefix_width) + (d if include_input else 0) + 2 * d * F
+
+
+def posenc_forward(coords, bands, prefix=None, include_input=True, out=None):
+    """The row ``[prefix | coords | sin(coords * bands) | cos(coords * bands)]`` fp32 [N, P + E] in one kernel (the layout of the
+    reference's PositionalEmbedder behind the ``P`` prefix columns). ``out``: an fp32 [N, P + E] tensor or row-strided view to
+    write into (columns of its storage beyond P + E are left alone); a new tensor otherwise."""
+    coords, cs = _posenc_rows(coords, None, "coords")
+    N, d = coords.shape
+    P = 0 if prefix is None else int(prefix.shape[-1])
+    bands = bands.detach().contiguous()
+    F, width = _posenc_shape(d, bands, include_input, P)
+    dev = coords.device
+    ps = 0
+    if prefix is not None:
+        prefix, ps = _posenc_rows(prefix, P, "prefix")
+        if prefix.shape[0] != N or prefix.device != dev:
+            raise RuntimeError(f"shacira_amd: posenc prefix {tuple(prefix.shape)} on {prefix.device} for coords {(N, d)} on {dev}")
+    if bands.device != dev:
+        raise RuntimeError("shacira_amd: posenc bands and coords are on different devices")
+    if out is None:
+        out = torch.empty((N, width), dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, width)
+          or (width > 1 and out.stride(1) != 1) or (N > 1 and out.stride(0) < width)):
+        raise RuntimeError(f"shacira_amd: posenc out must be fp32 [{N}, {width}] on {dev} with unit column stride")
+    if N == 0:
+        return out
+    os_ = out.stride(0) if N > 1 else width
+    with _on_device(dev):
+        rc = _lib.lib().shacira_posenc_forward(N, d, F, int(bool(include_input)), P, _ptr(coords), cs,
+                                               _ptr(prefix) if P > 0 else None, ps, _ptr(bands), _ptr(out), os_,
+                                               _stream(coords))
+    _lib.check(rc, "posenc_forward")
+    return out
+
+
+def posenc_backward(row, grad_out, bands, d, include_input=True, prefix_width=0):
+    """grad_coords fp32 [N, d] of ``posenc_forward`` from its SAVED output ``row`` and ``grad_out`` (both [N, P + E])."""
+    bands = bands.detach().contiguous()
+    F, width = _posenc_shape(int(d), bands, include_input, prefix_width)
+    row, rs = _posenc_rows(row, width, "row")
+    grad_out, gs = _posenc_rows(grad_out, width, "grad_out")
+    N, dev = row.shape[0], row.device
+    if grad_out.shape[0] != N or grad_out.device != dev or bands.device != dev:
+        raise RuntimeError("shacira_amd: posenc_backward operands disagree in rows or device")
+    grad_coords = torch.empty((N, int(d)), dtype=torch.float32, device=dev)
+    if N == 0:
+        return grad_coords
+    with _on_device(dev):
+        rc = _lib.lib().shacira_posenc_backward(N, int(d), F, int(bool(include_input)), int(prefix_width), _ptr(row), rs,
+                                                _ptr(grad_out), gs, _ptr(bands), _ptr(grad_coords), _stream(row))
+    _lib.check(rc, "posenc_backward")
+    return grad_coords
+
+
+def posenc_backward2(gg, row, grad_out, bands, d, include_input=True, prefix_width=0):
+    """(grad_row, grad_grad_out), both fp32 [N, P + E]: the gradients of ``(posenc_backward(row, grad_out) * gg).sum()`` with
+    respect to ``row`` and to ``grad_out``."""
+    bands = bands.detach().contiguous()
+    F, width = _posenc_shape(int(d), bands, include_input, prefix_width)
+    row, rs = _posenc_rows(row, width, "row")
+    grad_out, gs = _posenc_rows(grad_out, width, "grad_out")
+    gg, _ = _posenc_rows(gg, int(d), "gg")
+    gg = gg.contiguous()
+    N, dev = row.shape[0], row.device
+    if grad_out.shape[0] != N or gg.shape[0] != N or grad_out.device != dev or gg.device != dev or bands.device != dev:
+        raise RuntimeError("shacira_amd: posenc_backward2 operands disagree in rows or device")
+    grad_row = torch.empty((N, width), dtype=torch.float32, device=dev)
+    grad_grad = torch.empty((N, width), dtype=torch.float32, device=dev)
+    if N == 0:
+        return grad_row, grad_grad
+    with _on_device(dev):
+        rc = _lib.lib().shacira_posenc_backward2(N, int(d), F, int(bool(include_input)), int(prefix_width), _ptr(gg), _ptr(row),
+                                                 rs, _ptr(grad_out), gs, _ptr(bands), _ptr(grad_row), _ptr(grad_grad),
+                                                 _stream(row))
+    _lib.check(rc, "posenc_backward2")
+    return grad_row, grad_grad

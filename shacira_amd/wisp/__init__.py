@@ -16,7 +16,8 @@ _ALIASES = [
     "models.latent_decoders.basic_latent_decoder", "models.latent_decoders.hierarchical_latent_decoder",
     "models.latent_decoders.multi_latent_decoder",
     "models.prob_models", "models.prob_models.bit_estimator", "models.decoders", "models.decoders.basic_decoders",
-    "models.embedders", "models.nefs", "models.nefs.nerf", "models.nefs.neural_sdf", "tracers", "tracers.packed_rf_tracer",
+    "models.embedders", "models.activations", "models.nefs", "models.nefs.image", "models.nefs.nerf", "models.nefs.neural_sdf",
+    "tracers", "tracers.packed_rf_tracer",
     "tracers.packed_sdf_tracer", "utils", "utils.schedulers",
 ]
 

@@ -1,5 +1,6 @@
+from .image import NeuralImage
 from .nerf import NeuralRadianceField
 from .neural_sdf import NeuralSDF
 from .neural_sdf_tex import NeuralSDFTex
 
-__all__ = ["NeuralRadianceField", "NeuralSDF", "NeuralSDFTex"]
+__all__ = ["NeuralImage", "NeuralRadianceField", "NeuralSDF", "NeuralSDFTex"]
