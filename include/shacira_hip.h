@@ -677,6 +677,51 @@ SHACIRA_API int shacira_posenc_backward2(int64_t n, int d, int num_bands, int in
                                          void *stream);
 
 /*
+ * Ray generation: origins, unit directions and composited target colours of n (view, pixel) pairs in one kernel, from one
+ * small record per camera and the uint8 training images -- what wisp/ops/raygen/raygen.py:46-119 computes per view and
+ * wisp/datasets/formats/nerf_standard_dataset.py:407-428 stores for every pixel of every view. Not differentiable.
+ *   cams           fp32 [num_views, SHACIRA_RAYGEN_RECORD_FLOATS] on the device, 16-byte aligned; one record, rounded from the
+ *                  fp64 camera:
+ *                     0 ..  8   R, the camera-to-world rotation, row-major (the transpose of the view matrix's 3x3)
+ *                     9 .. 11   t, the camera's position in the world
+ *                    12, 13     tan of half the horizontal / vertical field of view: W / (2 fx), H / (2 fy)
+ *                    14, 15     x0, y0: the principal point as an offset in pixels from the image centre
+ *                    16         lens: 0 pinhole, anything else orthographic
+ *                    17, 18     fov_distance * (W / H), fov_distance (orthographic lens)
+ *                    19         reserved, 0
+ *   width, height  W, H of every view, both > 0, W * H < 2^31
+ *   view_idx, pixel_idx   int32 [n], pixel = y * W + x. Both NULL: the whole-view form, ray i is pixel i mod (H W) of view
+ *                  i div (H W) and n <= num_views * H * W
+ *   jitter         fp32 [n, 2] (jx, jy), 8-byte aligned, or NULL: a sub-pixel offset added to the pixel centre
+ *   images         uint8 [num_views, H, W, channels], channels 3 or 4; NULL: rgb and mask are not written (and may be NULL)
+ *   bg_mode        SHACIRA_RAYGEN_BG_WHITE / _BLACK: what a 4-channel image is composited over
+ *   origins, dirs, rgb   fp32 [n, 3] dense; mask uint8 [n], 0 or 1
+ * fp32, one rounding per operator, in this order (correctly rounded / and sqrt, no fused multiply-add):
+ *     px = ((x + 0.5) + jx) - x0        py = ((y + 0.5) + jy) + y0        (the orthographic lens skips x0 and y0, as the
+ *     u  = 2 (px / W) - 1               v  = 2 (py / H) - 1                reference's generate_ortho_rays does)
+ *     pinhole        d_cam = (u tanx, -v tany, -1)       origin = t, the record's bits
+ *     orthographic   d_cam = (0, 0, -1)                  o_cam = (u fd aspect, -v fd, 0),  origin_i = (R_i0 o_x + R_i1 o_y) + t_i
+ *     w_i = (R_i0 d_x + R_i1 d_y) + R_i2 d_z             dirs = w / sqrt((w_x^2 + w_y^2) + w_z^2)
+ *     c = float(byte) / 255,  a likewise
+ *     3 channels     rgb = c, mask = 1
+ *     white          rgb = clamp(c * a + (1 - a), 0, 1)        black   rgb = clamp(c - (1 - a), 0, 1)        mask = a > 0.5
+ * A ray whose view index is outside [0, num_views) or whose pixel index is outside [0, H W) reads nothing and gets NaN in its
+ * rows of origins, dirs and rgb and 0 in mask; every other ray is unaffected. One lane makes one ray; no workspace, no
+ * allocation, no synchronisation, no atomics: capturable, and two calls return the same bits. Validation precedes any HIP call:
+ * SHACIRA_EINVAL for num_views, width or height <= 0, W * H >= 2^31, n < 0, channels outside {3, 4} with images, an unknown
+ * bg_mode, only one of the two index arrays, n > num_views * H * W in the whole-view form, NULL cams / origins / dirs (rgb /
+ * mask with images), or a misaligned cams / jitter. n == 0 returns 0 with nothing enqueued, whatever the pointers (the sizes,
+ * channels and bg_mode are checked first).
+ */
+#define SHACIRA_RAYGEN_RECORD_FLOATS 20
+#define SHACIRA_RAYGEN_BG_WHITE 0
+#define SHACIRA_RAYGEN_BG_BLACK 1
+SHACIRA_API int shacira_raygen_record_floats(void);
+SHACIRA_API int shacira_raygen(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                               const int32_t *pixel_idx, const float *jitter, int64_t n, const uint8_t *images, int channels,
+                               int bg_mode, float *origins, float *dirs, float *rgb, uint8_t *mask, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

@@ -599,6 +599,25 @@ int shacira_ssim_backward(int64_t height, int64_t width, int pixel_stride, int c
                                        (hipStream_t)stream);
 }
 
+// ---- ray generation -------------------------------------------------------------------------------------------------------------
+int shacira_raygen_record_floats(void) { return SHACIRA_RAYGEN_RECORD_FLOATS; }
+
+int shacira_raygen(const float *cams, int num_views, int width, int height, const int32_t *view_idx, const int32_t *pixel_idx,
+                   const float *jitter, int64_t n, const uint8_t *images, int channels, int bg_mode, float *origins, float *dirs,
+                   float *rgb, uint8_t *mask, void *stream) {
+    if (num_views <= 0 || width <= 0 || height <= 0 || n < 0) return SHACIRA_EINVAL;
+    if ((int64_t)width * height > INT32_MAX) return SHACIRA_EINVAL;          // pixel indices are int32
+    if (images && channels != 3 && channels != 4) return SHACIRA_EINVAL;
+    if (bg_mode != SHACIRA_RAYGEN_BG_WHITE && bg_mode != SHACIRA_RAYGEN_BG_BLACK) return SHACIRA_EINVAL;
+    if ((view_idx == nullptr) != (pixel_idx == nullptr)) return SHACIRA_EINVAL;
+    if (!view_idx && n > (int64_t)num_views * ((int64_t)width * height)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;                       // an empty batch may come with NULL operands
+    if (!cams || !origins || !dirs || (images && (!rgb || !mask))) return SHACIRA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(cams) & 15u) != 0 || (reinterpret_cast<uintptr_t>(jitter) & 7u) != 0) return SHACIRA_EINVAL;
+    return (int)raygen_dispatch(cams, num_views, width, height, view_idx, pixel_idx, jitter, n, images, channels,
+                                bg_mode == SHACIRA_RAYGEN_BG_BLACK, origins, dirs, rgb, mask, (hipStream_t)stream);
+}
+
 // ---- positional-encoding rows ----------------------------------------------------------------------------------------------
 // the shape shared by the three calls; `width` = P + E. Row strides are checked by the callers
 static bool posenc_shape_ok(int64_t n, int d, int num_bands, int64_t prefix_width, int64_t *width) {

@@ -173,6 +173,12 @@ hipError_t posenc_backward2_dispatch(int64_t n, int d, int F, int I, int P, cons
                                      const float *grad_out, int64_t gstride, const float *bands, float *grad_row,
                                      float *grad_grad, hipStream_t s);
 
+// raygen.hip: rays and composited target colours of (view, pixel) pairs (arguments checked by the entry point; view_idx == NULL is
+// the whole-view form; images == NULL: no rgb, no mask)
+hipError_t raygen_dispatch(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                           const int32_t *pixel_idx, const float *jitter, int64_t n, const uint8_t *images, int channels,
+                           bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s);
+
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
                                    const float *depth, int32_t *out, hipStream_t s);

@@ -792,3 +792,118 @@ def fit_nerf(device, steps=300, rays=4096, num_steps=128, seed=0, codebook_bitwi
         out.update(table_bytes_fp32=grid.codebook.numel() * 4, latent_bytes_estimate=latent_bits / 8,
                    file_bytes=len(codec.save_model(nef)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ multiview datasets
+def _analytic_truth(blas_level=5):
+    from .wisp.models.grids import HashGrid
+    return _AnalyticNef(HashGrid.from_geometric(feature_dim=2, num_lods=2, multiscale_type="cat", resolution_dim=3,
+                                                feature_std=0.0, codebook_bitwidth=4, min_grid_res=2, max_grid_res=4,
+                                                blas_level=blas_level))   # carries the occupancy only
+
+
+def write_analytic_dataset(path, views, height, width, seed=0, device="cuda", split="train", num_steps=256,
+                           camera_angle_x=0.6911):
+    """Write a NeRF-synthetic style dataset of the closed-form scene into ``path``: ``views`` RGBA PNGs of height x width under
+    ``{split}/`` and ``transforms_{split}.json``. The cameras sit on the radius-3 sphere and look at the origin; their poses
+    are written in Blender's convention (z up, camera-to-world), so a loader has to change coordinates to get the y-up world the
+    scene lives in. Images are rendered by PackedRFTracer through wisp.ops.raygen's rays with exactly the pose handling of
+    ``wisp.datasets.NeRFSyntheticDataset``; the PNG keeps the straight colour and the alpha, so compositing it over white gives
+    the render back to within the 8-bit quantisation. Returns the list of image paths."""
+    import json
+    import os
+    from PIL import Image
+    from .wisp.core import Camera, blender_coords
+    from .wisp.ops.raygen import generate_rays
+    from .wisp.tracers import PackedRFTracer
+    device = torch.device(device)
+    gen = torch.Generator().manual_seed(seed)
+    eye = torch.randn(views, 3, generator=gen, dtype=torch.float64)
+    eye[:, 2] = eye[:, 2].abs() * 0.5 + 0.2                      # upper hemisphere, off the pole
+    eye = 3.0 * eye / eye.norm(dim=1, keepdim=True)
+    back = eye / eye.norm(dim=1, keepdim=True)
+    right = torch.linalg.cross(torch.tensor([[0.0, 0.0, 1.0]], dtype=torch.float64).expand_as(back), back)
+    right = right / right.norm(dim=1, keepdim=True)
+    up = torch.linalg.cross(back, right)
+    poses = torch.zeros(views, 4, 4, dtype=torch.float64)
+    poses[:, :3, 0], poses[:, :3, 1], poses[:, :3, 2], poses[:, :3, 3], poses[:, 3, 3] = right, up, back, eye, 1.0
+    view = torch.zeros_like(poses)
+    view[:, :3, :3] = poses[:, :3, :3].transpose(1, 2)
+    view[:, :3, 3] = -(view[:, :3, :3] @ poses[:, :3, 3:4]).squeeze(-1)
+    view[:, 3, 3] = 1.0
+    fx = 0.5 * width / math.tan(0.5 * camera_angle_x)
+    cameras = Camera.from_args(view_matrix=view, focal_x=fx, width=width, height=height, near=0.0, far=6.0)
+    cameras.change_coordinate_system(blender_coords())
+    cameras = cameras.to(device)
+    truth, tracer = _analytic_truth(), PackedRFTracer(raymarch_type="ray", num_steps=num_steps, bg_color="white")
+    os.makedirs(os.path.join(path, split), exist_ok=True)
+    frames, files = [], []
+    with torch.no_grad():
+        for i in range(views):
+            rays, _, _ = generate_rays(cameras[i])
+            rb = tracer(truth, rays)
+            alpha = rb.alpha.clamp(0, 1)
+            straight = ((rb.rgb - (1.0 - alpha)) / alpha.clamp_min(1e-6)).clamp(0, 1)
+            rgba = (torch.cat([straight, alpha], -1) * 255.0).round().to(torch.uint8).reshape(height, width, 4).cpu().numpy()
+            files.append(os.path.join(path, split, f"r_{i}.png"))
+            Image.fromarray(rgba, "RGBA").save(files[-1])
+            frames.append(dict(file_path=f"./{split}/r_{i}", transform_matrix=poses[i].tolist()))
+    with open(os.path.join(path, f"transforms_{split}.json"), "w") as fh:
+        json.dump(dict(camera_angle_x=camera_angle_x, aabb_scale=1.0, frames=frames), fh, indent=1)
+    return files
+
+
+def evaluate_view(nef, tracer, dataset, i, chunk=4096):
+    """Render view ``i`` of a multiview dataset with ``tracer`` over ``nef`` and score it against the view's target image:
+    ``evaluate_image``'s dict plus the rendered image ``rgb`` [H, W, 3]. The whole view's rays are made once; the tracer walks
+    them in chunks of ``chunk`` rays (a host loop: the last chunk may be short)."""
+    from .wisp.core import Rays
+    item = dataset[i]
+    rays = item["rays"]
+    h, w = dataset.img_shape[:2]
+    out = []
+    with torch.no_grad():
+        for start in range(0, len(rays), chunk):
+            part = rays[start:start + chunk]
+            out.append(tracer(nef, Rays(part.origins, part.dirs, dist_min=rays.dist_min, dist_max=rays.dist_max)).rgb[..., :3])
+    pred = torch.cat(out).reshape(h, w, 3)
+    result = evaluate_image(pred.clamp(0, 1), item["rgb"].reshape(h, w, 3))
+    result["rgb"] = pred
+    return result
+
+
+def fit_multiview(dataset, device, steps=300, rays=4096, num_steps=128, seed=0, codebook_bitwidth=19, max_grid_res=2048,
+                  num_lods=16, blas_level=5, prune_every=100, hidden_dim=64, feature_dim=2):
+    """The eager step of ``fit_nerf`` fed by a multiview dataset: every step draws ``rays`` random pixels over all views with
+    ``dataset.sample`` -- rays and composited target colours made on the device by the ray kernel -- renders them through the
+    hash grid and takes an L1 / Adam step. Returns dict(nef, tracer, losses [steps] on the host, ms_per_step)."""
+    import time
+    from .optim import FusedAdam
+    from .wisp.models.grids import HashGrid
+    from .wisp.models.nefs import NeuralRadianceField
+    from .wisp.tracers import PackedRFTracer
+    torch.manual_seed(seed)
+    grid = HashGrid.from_geometric(feature_dim=feature_dim, num_lods=num_lods, multiscale_type="cat", resolution_dim=3,
+                                   feature_std=0.01, codebook_bitwidth=codebook_bitwidth, min_grid_res=16,
+                                   max_grid_res=max_grid_res, blas_level=blas_level)
+    nef = NeuralRadianceField(grid, view_embedder="positional", view_multires=4, hidden_dim=hidden_dim, num_layers=1,
+                              prune_density_decay=0.95, prune_min_density=0.01 * 512 / 3 ** 0.5).to(device)
+    tracer = PackedRFTracer(raymarch_type="ray", num_steps=num_steps, bg_color=dataset.bg_color)
+    opt = FusedAdam([g for g in param_groups(nef, lr=1e-3, grid_lr=1e-2) if g["params"]], eps=1e-15)
+    gen = torch.Generator(device=device).manual_seed(seed + 1)
+    losses = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(steps):
+        batch = dataset.sample(rays, generator=gen)
+        opt.zero_grad(set_to_none=True)
+        rb = tracer(nef, batch["rays"])
+        loss = torch.abs(rb.rgb[..., :3] - batch["rgb"]).mean()
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+        if prune_every and (it + 1) % prune_every == 0:
+            nef.prune()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / max(1, steps) * 1e3
+    return dict(nef=nef, tracer=tracer, losses=torch.stack(losses).cpu(), ms_per_step=ms, steps=steps, rays_per_step=rays)

@@ -1248,3 +1248,57 @@ def posenc_backward2(gg, row, grad_out, bands, d, include_input=True, prefix_wid
                                                  _stream(row))
     _lib.check(rc, "posenc_backward2")
     return grad_row, grad_grad
+
+
+# ---- ray generation (include/shacira_hip.h, shacira_raygen) ---------------------------------------------------------------------
+def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white", num_rays=None):
+    """(origins, dirs, rgb, mask) of (view, pixel) pairs in one kernel: fp32 [n, 3] each and bool [n, 1]; ``rgb`` and ``mask``
+    are None without ``images``. ``records``: fp32 [V, RAYGEN_RECORD_FLOATS] camera records; ``view_idx`` / ``pixel_idx``: int32
+    [n] (pixel = y * W + x), or both None for the whole-view form -- ray i is pixel i mod (H W) of view i div (H W), for the first
+    ``num_rays`` rays (default: all V H W); ``jitter``: fp32 [n, 2] or None; ``images``: uint8 [V, H, W, 3 or 4] or None.
+    An index out of range gives a NaN row and mask 0. Not differentiable."""
+    _need_gpu(records, view_idx, pixel_idx, jitter, images)
+    dev = records.device
+    K = _lib.RAYGEN_RECORD_FLOATS
+    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != K or not records.is_contiguous():
+        raise RuntimeError(f"shacira_amd: raygen expects contiguous fp32 records [V, {K}], got {records.dtype} "
+                           f"{tuple(records.shape)}")
+    V, W, H = records.shape[0], int(width), int(height)
+    if bg_color not in ("white", "black"):
+        raise RuntimeError(f"shacira_amd: raygen bg_color must be 'white' or 'black', got {bg_color!r}")
+    if (view_idx is None) != (pixel_idx is None):
+        raise RuntimeError("shacira_amd: raygen takes view_idx and pixel_idx together, or neither")
+    if view_idx is None:
+        n = V * H * W if num_rays is None else int(num_rays)
+    else:
+        for name, t in (("view_idx", view_idx), ("pixel_idx", pixel_idx)):
+            if t.dtype != torch.int32 or t.dim() != 1 or t.device != dev:
+                raise RuntimeError(f"shacira_amd: raygen expects int32 [n] {name} on {dev}, got {t.dtype} {tuple(t.shape)} "
+                                   f"on {t.device}")
+        n = view_idx.shape[0]
+        if pixel_idx.shape[0] != n or (num_rays is not None and int(num_rays) != n):
+            raise RuntimeError("shacira_amd: raygen view_idx, pixel_idx and num_rays disagree")
+        view_idx, pixel_idx = view_idx.contiguous(), pixel_idx.contiguous()
+    if jitter is not None:
+        if jitter.dtype != torch.float32 or tuple(jitter.shape) != (n, 2) or jitter.device != dev:
+            raise RuntimeError(f"shacira_amd: raygen expects fp32 jitter [{n}, 2] on {dev}")
+        jitter = jitter.detach().contiguous()
+    channels = 4
+    if images is not None:
+        if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[:3]) != (V, H, W) or images.device != dev:
+            raise RuntimeError(f"shacira_amd: raygen expects uint8 images [{V}, {H}, {W}, C] on {dev}, got {images.dtype} "
+                               f"{tuple(images.shape)} on {images.device}")
+        images = images.contiguous()
+        channels = images.shape[3]
+    origins = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    dirs = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    rgb = mask = None
+    if images is not None:
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        mask = torch.empty((n, 1), dtype=torch.bool, device=dev)
+    with _on_device(dev):
+        rc = _lib.lib().shacira_raygen(_ptr(records), V, W, H, _ptr(view_idx), _ptr(pixel_idx), _ptr(jitter), n, _ptr(images),
+                                       channels, _lib.RAYGEN_BG_BLACK if bg_color == "black" else _lib.RAYGEN_BG_WHITE,
+                                       _ptr(origins), _ptr(dirs), _ptr(rgb), _ptr(mask), _stream(records))
+    _lib.check(rc, "raygen")
+    return origins, dirs, rgb, mask

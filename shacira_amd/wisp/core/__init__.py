@@ -45,3 +45,6 @@ class RenderBuffer:
         self.rgb, self.alpha, self.depth, self.hit = rgb, alpha, depth, hit
         for k, v in extra.items():
             setattr(self, k, v)
+
+
+from .camera import Camera, CameraFOV, blender_coords  # noqa: E402,F401
