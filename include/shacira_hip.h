@@ -153,6 +153,9 @@ SHACIRA_API int shacira_hashgrid_backward_levels(int dim, int64_t num_coords, in
  *                                    pixel lattice every step, wisp/trainers/image_trainer.py:234-266) may keep it across
  *                                    steps and pass plan_flags = SHACIRA_PLAN_READY to the forward, which then skips its sort
  *   plan_bytes                       size of the buffer; SHACIRA_EWORKSPACE when it is non-NULL and too small
+ *   workspace (forward)              shacira_hashgrid_forward_workspace_bytes covers a call without a plan buffer, which keeps
+ *                                    its plan inside the workspace; a forward that brings its plan buffer (plan != NULL, a shape
+ *                                    that sorts) accepts a workspace shorter by shacira_hashgrid_plan_bytes
  *   shacira_hashgrid_backward_planned_workspace_bytes (ABI 11)
  *                                    scratch the planned backward of this shape needs: the levels its brick pass takes write no
  *                                    items and the others 12-byte units, S1 at 2^20 samples: 0.70 GB against the 1.10 GB of

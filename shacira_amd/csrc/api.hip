@@ -161,10 +161,11 @@ int shacira_hashgrid_forward_planned(int dim, int64_t num_coords, int num_lods, 
     if (num_coords < 0) return SHACIRA_EINVAL;
     if (num_coords == 0) return 0;
     if (!codebook_first_idx || !coords || !codebook || !feats) return SHACIRA_EINVAL;
-    const size_t need = hashgrid_forward_workspace(dim, dtype, lt, num_coords);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
     // a plan buffer is used only by the shapes that sort (shacira_hashgrid_plan_bytes > 0); others ignore it
     const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
+    // (a call that brings its plan buffer needs shacira_hashgrid_plan_bytes less than the workspace query says)
+    const size_t need = hashgrid_forward_workspace(dim, dtype, lt, num_coords, plan != nullptr && sorts);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
     if (plan != nullptr && sorts && plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
     if ((plan_flags & ~SHACIRA_PLAN_READY) != 0 || ((plan_flags & SHACIRA_PLAN_READY) != 0 && plan == nullptr)) return SHACIRA_EINVAL;
     return (int)hashgrid_forward_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, feats, workspace,

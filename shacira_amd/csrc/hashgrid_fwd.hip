@@ -963,9 +963,9 @@ static hipError_t launch_fwd_f64(const LevelTable &lt, const int32_t *first_idx,
     return hipSuccess;
 }
 
-size_t hashgrid_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n) {
+size_t hashgrid_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n, bool caller_plan) {
     if (dtype == SHACIRA_F64) return 0;
-    if (tiled_supported(dim, dtype, lt, n)) return tiled_forward_workspace(dim, dtype, lt, n);
+    if (tiled_supported(dim, dtype, lt, n)) return tiled_forward_workspace(dim, dtype, lt, n, caller_plan);
     if (lt.feature_dim != 2 && lt.feature_dim != 4) return 0;
     if (use_lds_tables(dim, dtype == SHACIRA_F32 ? 4 : 2, lt, n)) return 0;   // variant 9 stages nothing
     size_t b = ((size_t)n * lt.num_lods * lt.feature_dim * (dtype == SHACIRA_F32 ? 4 : 2) + 255) / 256 * 256;

@@ -11,7 +11,7 @@
 // block ("coarse" levels: 0-7 of S1), so walking the samples block by block turns those levels' gathers into L1 hits.
 // Levels finer than that (one sample per cell: no reuse possible in any order) keep the level-per-XCD pair kernel.
 //
-//   sort      counting sort of the samples by block id (two partitioning passes, three launches: psort_*) -> 16-byte records
+//   sort      counting sort of the samples by block id (two partitioning passes, two launches: psort_*) -> 16-byte records
 //             {coordinates (exact copies), sample index} + block offsets = the batch's PLAN, which the backward can reuse
 //   fine      hashgrid_fwd_level_pair_kernel over the sorted coordinates, levels [lc, L) -> staging [L][N][F]
 //   rows      hashgrid_fwd_rows_kernel: coarse levels [0, lc) over the sorted coordinates (lane pairs, L1-resident
@@ -52,16 +52,19 @@ struct TilePlan {
     // partition sort: coarse bin = block id >> coarse_shift (a contiguous range of <= 16 blocks); tiles of whole chunks
     uint32_t coarse_shift, num_coarse;
     uint32_t ptiles, chunks_per_tile;
+    // per-(tile, block) counts of the first pass: elements per tile row (num_blocks rounded up to 64) and their width
+    uint32_t bcnt_stride, bcnt16;
 };
 
 struct TileCtx {            // device pointers into the sort's outputs (the plan) and its scratch
     uint32_t *header;       // [0] magic, [1] num_blocks, [2] n
     float4 *sorted4;        // [n] sample records in sorted order: {x, y, z (0 in 2-D) -- exact copies --, bits of the sample index}
     uint32_t *block_start;  // [num_blocks + 1]
-    uint32_t *cnt;          // scratch: [ptiles][kMaxCoarse] samples per (tile, coarse bin)
-    float4 *inter4;         // scratch: [n] records grouped by coarse bin
-    uint32_t *gcursor;      // scratch: [2][kMaxBlocksS] per-block cursors | per-block counts of over-full bins
-    uint32_t *cbase;        // scratch: [kMaxCoarse + 1] first record of every coarse bin
+    uint32_t *cnt;          // scratch: [kMaxCoarse][kMaxSortTiles] samples per (coarse bin, tile)
+    uint32_t *coff;         // scratch: [kMaxCoarse][kMaxSortTiles] where a bin's run starts inside a tile's region
+    float4 *inter4;         // scratch: [n] records grouped by tile, then by coarse bin
+    void *bcnt;             // scratch: [ptiles][bcnt_stride] samples per (tile, block), 16- or 32-bit (TilePlan::bcnt16)
+    uint32_t *gcursor;      // scratch: [kMaxBlocksS] per-block cursors of over-full bins
 };
 
 static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
@@ -112,6 +115,8 @@ static void make_sort_plan(int dim, int64_t n, TilePlan &tp) {
     tp.chunks_per_tile = (uint32_t)((chunks + kMaxSortTiles - 1) / kMaxSortTiles);
     if (tp.chunks_per_tile < 1) tp.chunks_per_tile = 1;
     tp.ptiles = (uint32_t)((chunks + tp.chunks_per_tile - 1) / tp.chunks_per_tile);
+    tp.bcnt_stride = (tp.num_blocks + 63u) / 64u * 64u;
+    tp.bcnt16 = (uint64_t)kSortTileS * tp.chunks_per_tile < 65536u ? 1u : 0u;   // a tile's count of one block fits 16 bits
 }
 
 static void make_tile_plan(int dim, const LevelTable &lt, int64_t n, TilePlan &tp) {
@@ -152,18 +157,21 @@ static size_t carve_plan(int64_t n, void *buf, TileCtx &c) {
     return off;
 }
 static size_t carve_scratch(int dim, int64_t n, void *buf, TileCtx &c) {
-    (void)dim;
+    TilePlan tp;
+    make_sort_plan(dim, n, tp);
     size_t off = 0;
     auto take = [&](size_t b) { size_t o = off; off = up256(off + b); return o; };
     const size_t o_cnt = take((size_t)kMaxSortTiles * kMaxCoarse * 4);
+    const size_t o_coff = take((size_t)kMaxSortTiles * kMaxCoarse * 4);
     const size_t o_inter = take((size_t)n * sizeof(float4));
-    const size_t o_cb = take((size_t)(kMaxCoarse + 1) * 4);
-    const size_t o_gc = take((size_t)2 * kMaxBlocksS * 4);   // per-block cursors | per-block counts of over-full bins
+    const size_t o_bc = take((size_t)tp.ptiles * tp.bcnt_stride * (tp.bcnt16 ? 2 : 4));
+    const size_t o_gc = take((size_t)kMaxBlocksS * 4);
     unsigned char *p = static_cast<unsigned char *>(buf);
     if (p) {
         c.cnt = reinterpret_cast<uint32_t *>(p + o_cnt);
+        c.coff = reinterpret_cast<uint32_t *>(p + o_coff);
         c.inter4 = reinterpret_cast<float4 *>(p + o_inter);
-        c.cbase = reinterpret_cast<uint32_t *>(p + o_cb);
+        c.bcnt = p + o_bc;
         c.gcursor = reinterpret_cast<uint32_t *>(p + o_gc);
     }
     return off;
@@ -177,23 +185,30 @@ static size_t scratch_bytes_of(int dim, int64_t n) {
     return carve_scratch(dim, n, nullptr, c);
 }
 
-// ----------------------------------------------------------------------------------------------- partition sort (round 6)
-// Counting sort by block id in two partitioning passes, every write stream private to one workgroup:
-//   count       per tile of whole 4 096-sample chunks: samples per COARSE bin (<= 256 contiguous ranges of <= 16 block ids)
-//   partition   the same tiles: bin bases + this tile's offsets from the count matrix (column sums, no atomics, no scan
-//               launch), then each record goes to its bin's next slot (LDS returning atomic = final position)
-//   local       one workgroup per coarse bin keeps the bin's records in registers (<= 8 192; ~5 500 on a uniform batch): the
-//               returning LDS atomic that counts a record per (block, sub-cell of the block) is its rank; offsets = scan of
-//               <= 1 024 counts; the records go out run by run (a few KB each, written by one workgroup) and the bin's
-//               block offsets with them
-//   over-full bins (a batch concentrated in few blocks): `partition` also counts such a bin's records per block (global
-//               counters; one LDS flag decides, a uniform batch skips it); in `local` workgroup `bin` takes the bin's first
-//               8 192 records and one more workgroup per 8 192-aligned window of the partitioned batch takes what the bin holds
-//               beyond (surplus ones leave at once); each ranks its records in LDS and reserves one range per block from
-//               global cursors. Block order only in such bins. A Gaussian blob / a thin slab / one block of 2^20 samples
-//               sort as fast as a uniform batch (tools/skew_check.py: forward 0.29 / 0.26 / 0.22 ms against 0.29)
-// The round-5 sort it replaces (four launches) wrote every record straight to its block's slot: 2^20 scattered 16-byte stores into lines
-// shared by 256 workgroups (25 us of its 47). Order inside a block is arbitrary in both (ranks come from atomics).
+// ----------------------------------------------------------------------------------------------- partition sort
+// Counting sort by block id in two partitioning passes = two launches, every write stream private to one workgroup and no
+// workgroup waiting on another:
+//   partition   per tile of whole 4 096-sample chunks, nothing read but the coordinates: the returning LDS atomic that counts a
+//               record into its COARSE bin (<= 256 contiguous ranges of <= 16 block ids) is its rank inside (tile, bin); a scan
+//               of the 256 counts gives the tile's own bin offsets, and the record goes to inter4[tile's region + bin offset +
+//               rank]: grouped by tile, then by bin. The tile leaves its column of the count matrix cnt[bin][tile], of the
+//               offset matrix coff[bin][tile] (its own bin offsets) and its counts per BLOCK (bcnt[tile][block]) behind. A tile
+//               of several chunks sweeps them twice, counting then placing; the chunk it keeps in registers is counted last,
+//               behind a barrier, so its ranks follow the other chunks' slots.
+//   local       workgroup `bin` reads the bin's row of both matrices, nothing else: coff[bin][tile] is where the bin's run
+//               starts inside that tile's region and, summed over the tiles, the bin's first record; the row of counts, scanned
+//               over the tiles, maps "k-th record of the bin" to (tile, offset)
+//               -- a nine-step search in a 512-entry LDS prefix per record. The bin's <= 8 192 records (~5 500 on a uniform
+//               batch, from <= 512 runs of ~16) are then kept in registers: the returning LDS atomic that counts a record per
+//               (block, sub-cell of the block) is its rank; offsets = scan of <= 1 024 counts; the records go out run by run
+//               and the bin's block offsets with them
+//   over-full bins (a batch concentrated in few blocks): workgroup `bin` takes the bin's first 8 192 records and one more
+//               workgroup per 8 192-aligned window of the batch in bin-major order (a bin's records: its runs in tile order)
+//               takes what the bin holds beyond; a window's workgroup finds its bin from the row totals of the whole matrix
+//               (surplus ones leave after that sweep). Each sums the bin's columns of bcnt to the bin's block offsets, ranks
+//               its records in LDS and reserves one range per block from global cursors. Block order only in such bins.
+// The three-launch form before it (count, partition, local) read the whole count matrix in every tile of its second launch
+// before a record could be placed (profiles/sort_two_pass.md). Order inside a sub-cell is arbitrary (ranks come from atomics).
 template <int DIM>
 __device__ __forceinline__ void load_chunk_coords(const float *__restrict__ coords, int64_t s0, int64_t N,
                                                   float (&c)[kSortTileS / kSortThreadsS][DIM]) {
@@ -211,88 +226,67 @@ constexpr int kLocalR = 8;                                   // records a thread
 constexpr uint32_t kLocalCap = kLocalR * kSortThreadsS;      // a bin of <= 8 192 records is one chunk: read once, ranked in LDS
 
 template <int DIM>
-__global__ __launch_bounds__(kSortThreadsS) void psort_count_kernel(TilePlan tp, const float *__restrict__ coords,
-                                                                    int64_t N, uint32_t *__restrict__ cnt,
-                                                                    uint32_t *__restrict__ gcursor) {
-    __shared__ uint32_t s_hist[kMaxCoarse];
-    if (threadIdx.x < kMaxCoarse) s_hist[threadIdx.x] = 0;
-    // (the per-block cursors | counts of over-full bins start at zero: cleared here, one launch ahead of their first use)
-    if (blockIdx.x == 0)
-        for (uint32_t k = threadIdx.x; k < 2u * kMaxBlocksS; k += kSortThreadsS) gcursor[k] = 0u;
-    __syncthreads();
+__device__ __forceinline__ void store_record(float4 *__restrict__ inter4, uint32_t pos, const float (&c)[DIM], int64_t i) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const f32x4 rec = {c[0], c[1], DIM == 3 ? c[DIM - 1] : 0.0f, __uint_as_float((uint32_t)i)};
+    *reinterpret_cast<f32x4 *>(inter4 + pos) = rec;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kSortThreadsS) void psort_partition_kernel(TilePlan tp, const float *__restrict__ coords,
+                                                                        int64_t N, uint32_t *__restrict__ cnt,
+                                                                        uint32_t *__restrict__ coff,
+                                                                        void *__restrict__ bcnt,
+                                                                        uint32_t *__restrict__ gcursor,
+                                                                        float4 *__restrict__ inter4) {
+    __shared__ uint32_t s_hist[kMaxCoarse], s_off[kMaxCoarse], s_cursor[kMaxCoarse];
+    __shared__ uint32_t s_wave[kMaxCoarse / 64];
+    __shared__ uint32_t s_blk[kMaxBlocksS];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int U = kSortTileS / kSortThreadsS;
-    for (uint32_t ch = 0; ch < tp.chunks_per_tile; ++ch) {
-        const int64_t s0 = ((int64_t)blockIdx.x * tp.chunks_per_tile + ch) * kSortTileS;
+    // this tile's first chunk (every tile has one: first_s0 < N): in flight while the counters are cleared
+    float c0[U][DIM];
+    const int64_t first_s0 = (int64_t)blockIdx.x * tp.chunks_per_tile * kSortTileS;
+    load_chunk_coords<DIM>(coords, first_s0, N, c0);
+    if (threadIdx.x < kMaxCoarse) s_hist[threadIdx.x] = 0u;
+    for (uint32_t k = threadIdx.x; k < tp.bcnt_stride; k += kSortThreadsS) s_blk[k] = 0u;
+    // (the per-block cursors of over-full bins start at zero: cleared here, one launch ahead of their use)
+    if (blockIdx.x == 0)
+        for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxBlocksS; k += kSortThreadsS) gcursor[k] = 0u;
+    __syncthreads();
+    // count: the chunks beyond the first (tiles of several chunks only), then the first one, whose ranks are kept
+    for (uint32_t ch = 1; ch < tp.chunks_per_tile; ++ch) {
+        const int64_t s0 = first_s0 + (int64_t)ch * kSortTileS;
         if (s0 >= N) break;
         float c[U][DIM];
         load_chunk_coords<DIM>(coords, s0, N, c);
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (s0 + u * kSortThreadsS + threadIdx.x < N) atomicAdd(&s_hist[block_key<DIM>(c[u], tp) >> tp.coarse_shift], 1u);
+            if (s0 + u * kSortThreadsS + threadIdx.x < N) {
+                const uint32_t key = block_key<DIM>(c[u], tp);
+                atomicAdd(&s_hist[key >> tp.coarse_shift], 1u);
+                atomicAdd(&s_blk[key], 1u);
+            }
+    }
+    // (the first chunk's ranks must lie behind EVERY count of the other chunks: no wave may draw one before all have counted)
+    if (tp.chunks_per_tile > 1u) __syncthreads();
+    uint32_t bin0[U], rank0[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const bool live = first_s0 + u * kSortThreadsS + threadIdx.x < N;
+        const uint32_t key = block_key<DIM>(c0[u], tp);
+        bin0[u] = key >> tp.coarse_shift;
+        rank0[u] = live ? atomicAdd(&s_hist[bin0[u]], 1u) : 0xFFFFFFFFu;
+        if (live) atomicAdd(&s_blk[key], 1u);
     }
     __syncthreads();
-    // bin-major: a bin's counts over the tiles are one contiguous row (the partition pass sums it with one load per lane)
-    if (threadIdx.x < kMaxCoarse) cnt[(size_t)threadIdx.x * kMaxSortTiles + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-template <int DIM>
-__global__ __launch_bounds__(kSortThreadsS) void psort_partition_kernel(TilePlan tp, const float *__restrict__ coords,
-                                                                        int64_t N, const uint32_t *__restrict__ cnt,
-                                                                        uint32_t *__restrict__ cbase,
-                                                                        uint32_t *__restrict__ gcursor,
-                                                                        float4 *__restrict__ inter4) {
-    __shared__ uint32_t s_cursor[kMaxCoarse], s_tot[kMaxCoarse], s_before[kMaxCoarse];
-    __shared__ uint32_t s_wave[kMaxCoarse / 64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int U = kSortTileS / kSortThreadsS;
-    // this tile's first chunk: in flight while the offsets below are computed
-    float c0[U][DIM];
-    const int64_t first_s0 = (int64_t)blockIdx.x * tp.chunks_per_tile * kSortTileS;
-    load_chunk_coords<DIM>(coords, first_s0 < N ? first_s0 : 0, N, c0);
-    // bin totals and this tile's offset inside every bin: a wave sums one bin's row of the count matrix (16-byte loads, four
-    // tiles per lane), 16 bins per wave, eight rows in flight
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    constexpr int kWaves = kSortThreadsS / 64, kBinsPerWave = kMaxCoarse / kWaves;
-    const bool wide = tp.ptiles > 256u;   // a second 256-tile half
-#ifndef SHACIRA_SORT_RB
-#define SHACIRA_SORT_RB 8
-#endif
-    constexpr int RB = SHACIRA_SORT_RB;
-#pragma unroll 1
-    for (int g = 0; g < kBinsPerWave; g += RB) {
-        u32x4 v[RB], w[RB];
-#pragma unroll
-        for (int k = 0; k < RB; ++k) {
-            const u32x4 *row = reinterpret_cast<const u32x4 *>(cnt + (size_t)(wave * kBinsPerWave + g + k) * kMaxSortTiles);
-            v[k] = row[lane];
-            w[k] = wide ? row[64 + lane] : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int k = 0; k < RB; ++k) {
-            uint32_t tot = 0, before = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t t0 = lane * 4u + (uint32_t)e, t1 = 256u + t0;
-                const uint32_t a = t0 < tp.ptiles ? v[k][e] : 0u, b2 = t1 < tp.ptiles ? w[k][e] : 0u;
-                tot += a + b2;
-                before += (t0 < blockIdx.x ? a : 0u) + (t1 < blockIdx.x ? b2 : 0u);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                tot += __shfl_xor(tot, off, 64);
-                before += __shfl_xor(before, off, 64);
-            }
-            if (lane == 0) {
-                s_tot[wave * kBinsPerWave + g + k] = tot;
-                s_before[wave * kBinsPerWave + g + k] = before;
-            }
-        }
-    }
-    __syncthreads();
+    // the tile's column of the count matrix (bin-major: a bin's counts over the tiles are one contiguous row) and the
+    // exclusive scan of its 256 counts
     const bool owner = threadIdx.x < kMaxCoarse;   // (whole waves)
-    uint32_t tot = 0;
+    uint32_t excl = 0;
     if (owner) {
-        tot = s_tot[threadIdx.x];
+        const uint32_t tot = s_hist[threadIdx.x];
+        cnt[(size_t)threadIdx.x * kMaxSortTiles + blockIdx.x] = tot;
         uint32_t incl = tot;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -300,75 +294,43 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_partition_kernel(TilePlan
             if (lane >= (uint32_t)off) incl += nbr;
         }
         if (lane == 63) s_wave[wave] = incl;
-        s_cursor[threadIdx.x] = incl - tot;   // exclusive inside the wave; the wave bases are added behind the barrier
+        excl = incl - tot;
+    }
+    // the tile's counts per block, two 16-bit counts to a word where a tile holds < 65 536 samples
+    if (tp.bcnt16) {
+        uint32_t *row = static_cast<uint32_t *>(bcnt) + (size_t)blockIdx.x * (tp.bcnt_stride / 2u);
+        for (uint32_t k = threadIdx.x; k < tp.bcnt_stride / 2u; k += kSortThreadsS) row[k] = s_blk[2u * k] | (s_blk[2u * k + 1u] << 16);
+    } else {
+        uint32_t *row = static_cast<uint32_t *>(bcnt) + (size_t)blockIdx.x * tp.bcnt_stride;
+        for (uint32_t k = threadIdx.x; k < tp.bcnt_stride; k += kSortThreadsS) row[k] = s_blk[k];
     }
     __syncthreads();
-    uint32_t base = 0;
     if (owner) {
+        uint32_t base = excl;
         for (uint32_t wv = 0; wv < wave; ++wv) base += s_wave[wv];
-        base += s_cursor[threadIdx.x];
-        if (blockIdx.x == 0) {
-            cbase[threadIdx.x] = base;
-            if (threadIdx.x == kMaxCoarse - 1) cbase[kMaxCoarse] = base + tot;
-        }
-    }
-    // Over-full bins (more records than the last pass keeps in one workgroup's registers: a batch concentrated in few blocks):
-    // their records are also counted per BLOCK here, so that the last pass can place every 8 192-record chunk of such a bin with
-    // its own workgroup straight away. A uniform batch has none and skips all of it (one LDS flag).
-    __shared__ uint32_t s_over_any;
-    __shared__ uint32_t s_blk[kMaxBlocksS];
-    if (threadIdx.x == 0) s_over_any = 0u;
-    __syncthreads();
-    if (owner) {
-        s_cursor[threadIdx.x] = base + s_before[threadIdx.x];
-        if (tot > kLocalCap) s_over_any = 1u;
-        s_tot[threadIdx.x] = tot > kLocalCap ? 1u : 0u;       // (from here on: the bin is over-full)
+        s_off[threadIdx.x] = base;
+        s_cursor[threadIdx.x] = base;
+        coff[(size_t)threadIdx.x * kMaxSortTiles + blockIdx.x] = base;   // (what the last pass would otherwise sum from cnt)
     }
     __syncthreads();
-    const bool over_any = s_over_any != 0u;
-    if (over_any) {
-        for (uint32_t k = threadIdx.x; k < tp.num_blocks; k += kSortThreadsS) s_blk[k] = 0u;
-        __syncthreads();
-    }
-    for (uint32_t ch = 0; ch < tp.chunks_per_tile; ++ch) {
+    // place: the chunks beyond the first draw their slots again (they fill a run from its start), the first chunk's records
+    // follow at the ranks they drew while counting
+    float4 *region = inter4 + first_s0;
+    for (uint32_t ch = 1; ch < tp.chunks_per_tile; ++ch) {
         const int64_t s0 = first_s0 + (int64_t)ch * kSortTileS;
         if (s0 >= N) break;
         float c[U][DIM];
-        if (ch == 0) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int a = 0; a < DIM; ++a) c[u][a] = c0[u][a];
-        } else {
-            load_chunk_coords<DIM>(coords, s0, N, c);
-        }
-        uint32_t pos[U];
+        load_chunk_coords<DIM>(coords, s0, N, c);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = s0 + u * kSortThreadsS + threadIdx.x;
-            const uint32_t key = block_key<DIM>(c[u], tp);
-            pos[u] = (i < N) ? atomicAdd(&s_cursor[key >> tp.coarse_shift], 1u) : 0xFFFFFFFFu;
-            if (over_any && i < N && s_tot[key >> tp.coarse_shift]) atomicAdd(&s_blk[key], 1u);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = s0 + u * kSortThreadsS + threadIdx.x;
-            if (pos[u] != 0xFFFFFFFFu) {
-                typedef float f32x4 __attribute__((ext_vector_type(4)));
-                const f32x4 rec = {c[u][0], c[u][1], DIM == 3 ? c[u][DIM - 1] : 0.0f, __uint_as_float((uint32_t)i)};
-#ifdef SHACIRA_SORT_NT
-                __builtin_nontemporal_store(rec, reinterpret_cast<f32x4 *>(inter4 + pos[u]));
-#else
-                *reinterpret_cast<f32x4 *>(inter4 + pos[u]) = rec;
-#endif
-            }
+            if (i < N) store_record<DIM>(region, atomicAdd(&s_cursor[block_key<DIM>(c[u], tp) >> tp.coarse_shift], 1u), c[u], i);
         }
     }
-    if (over_any) {
-        __syncthreads();
-        uint32_t *gcount = gcursor + kMaxBlocksS;
-        for (uint32_t k = threadIdx.x; k < tp.num_blocks; k += kSortThreadsS)
-            if (s_blk[k]) atomicAdd(&gcount[k], s_blk[k]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = first_s0 + u * kSortThreadsS + threadIdx.x;
+        if (rank0[u] != 0xFFFFFFFFu) store_record<DIM>(region, s_off[bin0[u]] + rank0[u], c0[u], i);
     }
 }
 
@@ -389,54 +351,149 @@ __device__ __forceinline__ uint32_t wave_rank_add(uint32_t *counters, uint32_t j
     return live ? atomicAdd(&counters[j], 1u) : 0u;
 }
 
-// Workgroups of the last pass. w < num_coarse: bin w -- all of it when it holds <= 8 192 records (every bin of a uniform batch:
-// nothing but the bin's two offsets is read before its records), its first 8 192 records otherwise. What an over-full bin (a
-// batch concentrated in few blocks) holds beyond is cut at the 8 192-aligned windows of the partitioned batch, and workgroup
-// num_coarse + v takes window v: the bin holding the window's first record is the only one whose remainder can reach into that
-// window (the next bin's remainder starts >= 8 192 records behind its own start). So such a batch gets as many workgroups as it
-// has 8 192-record pieces, whatever bin they fall into (round 6: the first form gave an over-full bin four workgroups that each
-// counted ALL of it -- 0.8 ms for a Gaussian blob of 2^20 samples, tools/skew_check.py), and no workgroup searches a list.
+// Row totals of the count matrix (records per coarse bin) -> s_tot[kMaxCoarse], by the whole workgroup: wave w takes rows w,
+// w + 16, ..., eight of them in flight, a lane four tiles of a row (eight when the batch has more than 256 tiles).
+__device__ __forceinline__ void bin_totals(const TilePlan &tp, const uint32_t *__restrict__ cnt, uint32_t *s_tot) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t kWaves = kSortThreadsS / 64;
+    constexpr int RB = 8;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool wide = tp.ptiles > 256u;   // a second 256-tile half
+#pragma unroll 1
+    for (uint32_t r0 = wave; r0 < (uint32_t)kMaxCoarse; r0 += kWaves * RB) {
+        u32x4 v[RB], w[RB];
+#pragma unroll
+        for (int k = 0; k < RB; ++k) {
+            const u32x4 *row = reinterpret_cast<const u32x4 *>(cnt + (size_t)(r0 + (uint32_t)k * kWaves) * kMaxSortTiles);
+            v[k] = row[lane];
+            w[k] = wide ? row[64 + lane] : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int k = 0; k < RB; ++k) {
+            uint32_t tot = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t t0 = lane * 4u + (uint32_t)e, t1 = 256u + t0;
+                tot += (t0 < tp.ptiles ? v[k][e] : 0u) + (t1 < tp.ptiles ? w[k][e] : 0u);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+            if (lane == 0) s_tot[r0 + (uint32_t)k * kWaves] = tot;
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t bcnt_at(const void *__restrict__ bcnt, const TilePlan &tp, uint32_t tile, uint32_t block) {
+    const size_t i = (size_t)tile * tp.bcnt_stride + block;
+    return tp.bcnt16 ? (uint32_t)static_cast<const uint16_t *>(bcnt)[i] : static_cast<const uint32_t *>(bcnt)[i];
+}
+
+// Workgroups of the last pass. w < num_coarse: bin w -- all of it when it holds <= 8 192 records (every bin of a uniform batch),
+// its first 8 192 records otherwise. What an over-full bin (a batch concentrated in few blocks) holds beyond is cut at the
+// 8 192-aligned windows of the batch in bin-major order, and workgroup num_coarse + v takes window v: the bin holding the
+// window's first record is the only one whose remainder can reach into that window (the next bin's remainder starts >= 8 192
+// records behind its own start). So such a batch gets as many workgroups as it has 8 192-record pieces, whatever bin they fall
+// into, and no workgroup searches a list.
 template <int DIM>
 __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp, const float4 *__restrict__ inter4,
-                                                                    const uint32_t *__restrict__ cbase,
-                                                                    const uint32_t *__restrict__ gcount,
+                                                                    const uint32_t *__restrict__ cnt,
+                                                                    const uint32_t *__restrict__ coff,
+                                                                    const void *__restrict__ bcnt,
                                                                     uint32_t *__restrict__ gcursor,
                                                                     float4 *__restrict__ sorted4,
                                                                     uint32_t *__restrict__ block_start,
                                                                     uint32_t *__restrict__ header, uint32_t n) {
     constexpr int kBpc = kMaxBlocksS / kMaxCoarse;   // blocks per coarse bin (<= 16)
     constexpr int R = kLocalR;
-    uint32_t bin, lo, hi, c_lo, c_hi;
+    constexpr uint32_t kScanWaves = kMaxSortTiles / 64;
+    __shared__ uint32_t s_pre[kMaxSortTiles];        // per tile: records of this bin in the earlier tiles
+    __shared__ uint32_t s_src[kMaxSortTiles];        // per tile: inter4 index of the bin's k-th record, less k
+    __shared__ uint32_t s_wrow[kScanWaves], s_wcol[kScanWaves];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool first = blockIdx.x < tp.num_coarse;
+    uint32_t bin = blockIdx.x, p0 = 0;
+    if (!first) {
+        p0 = (blockIdx.x - tp.num_coarse) * kLocalCap;      // window's first record
+        if (p0 >= n) return;
+        // the bin holding record p0: row totals of the whole matrix (rows >= num_coarse hold zeros), scanned
+        __shared__ uint32_t s_rowtot[kMaxCoarse], s_wtot4[kMaxCoarse / 64], s_le;
+        if (threadIdx.x == 0) s_le = 0u;
+        bin_totals(tp, cnt, s_rowtot);
+        __syncthreads();
+        uint32_t incl = 0, tot = 0;
+        if (threadIdx.x < kMaxCoarse) {   // (whole waves)
+            tot = s_rowtot[threadIdx.x];
+            incl = tot;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t nbr = __shfl_up(incl, off, 64);
+                if (lane >= (uint32_t)off) incl += nbr;
+            }
+            if (lane == 63) s_wtot4[wave] = incl;
+        }
+        __syncthreads();
+        if (threadIdx.x < kMaxCoarse) {
+            uint32_t base = incl - tot;   // first record of bin threadIdx.x
+            for (uint32_t wv = 0; wv < wave; ++wv) base += s_wtot4[wv];
+            const uint64_t le = __ballot(threadIdx.x < tp.num_coarse && base <= p0);
+            if (lane == 0 && le) atomicAdd(&s_le, (uint32_t)__popcll(le));
+        }
+        __syncthreads();
+        bin = s_le - 1u;                                    // (bin 0 starts at 0 <= p0)
+    }
+    // the bin's rows of the two matrices (a tile per thread of the first eight waves): its records per tile, and where its run
+    // starts inside each tile's region -- which, summed over the tiles, is also the number of records in the bins before it
+    const uint32_t t = threadIdx.x & (kMaxSortTiles - 1);
+    uint32_t rowv = cnt[(size_t)bin * kMaxSortTiles + t], colv = coff[(size_t)bin * kMaxSortTiles + t];
+    if (threadIdx.x >= (uint32_t)kMaxSortTiles || t >= tp.ptiles) rowv = colv = 0u;
+    uint32_t incl = rowv, csum = colv;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t nbr = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += nbr;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) csum += __shfl_xor(csum, off, 64);
+    if (wave < kScanWaves && lane == 63) {
+        s_wrow[wave] = incl;
+        s_wcol[wave] = csum;
+    }
+    __syncthreads();
+    uint32_t lo = 0, tot = 0, pre = incl - rowv;
+    for (uint32_t wv = 0; wv < kScanWaves; ++wv) {
+        const uint32_t rw = s_wrow[wv];
+        if (wv < wave) pre += rw;
+        tot += rw;
+        lo += s_wcol[wv];
+    }
+    const uint32_t hi = lo + tot;
+    if (threadIdx.x < (uint32_t)kMaxSortTiles) {
+        s_pre[t] = pre;                                     // (tiles >= ptiles: tot, beyond every record of the bin)
+        s_src[t] = t * tp.chunks_per_tile * (uint32_t)kSortTileS + colv - pre;
+    }
+    uint32_t c_lo, c_hi;
     if (first) {
-        bin = blockIdx.x;
-        lo = cbase[bin];
-        hi = cbase[bin + 1];
         c_lo = lo;
         c_hi = (lo + kLocalCap < hi) ? lo + kLocalCap : hi;
     } else {
-        const uint32_t p0 = (blockIdx.x - tp.num_coarse) * kLocalCap;      // window's first record
-        if (p0 >= n) return;
-        __shared__ uint32_t s_le;
-        if (threadIdx.x == 0) s_le = 0u;
-        __syncthreads();
-        uint32_t c = (threadIdx.x < tp.num_coarse && cbase[threadIdx.x] <= p0) ? 1u : 0u;   // (whole waves: kMaxCoarse = 256)
-        if (threadIdx.x < kMaxCoarse) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-            if ((threadIdx.x & 63u) == 0u && c) atomicAdd(&s_le, c);
-        }
-        __syncthreads();
-        bin = s_le - 1u;                                                    // (cbase[0] = 0 <= p0)
-        lo = cbase[bin];
-        hi = cbase[bin + 1];
         c_lo = (lo + kLocalCap > p0) ? lo + kLocalCap : p0;
         c_hi = (p0 + kLocalCap < hi) ? p0 + kLocalCap : hi;
         if (c_lo >= c_hi) return;
     }
+    __syncthreads();
+    // record at position p of the batch in bin-major order (lo <= p < hi; others: some record of the batch): the last tile whose
+    // prefix does not exceed p - lo holds it
+    auto fetch = [&](uint32_t p) {
+        const uint32_t k = p - lo;
+        uint32_t tl = 0;
+#pragma unroll
+        for (uint32_t step = kMaxSortTiles / 2; step > 0; step >>= 1)
+            if (s_pre[tl + step] <= k) tl += step;
+        const uint32_t a = s_src[tl] + k;
+        return inter4[a < n ? a : n - 1u];
+    };
     const uint32_t key0 = bin << tp.coarse_shift;
     const uint32_t bpc = 1u << tp.coarse_shift;
-    const uint32_t lane = threadIdx.x & 63;
     auto key_of = [&](const float4 &r) {
         float cc[DIM];
         cc[0] = r.x;
@@ -449,7 +506,7 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp,
         header[1] = tp.num_blocks;
         header[2] = n;
     }
-    if (first && hi - lo <= kLocalCap) {
+    if (first && tot <= kLocalCap) {
         // the usual case: every record of the bin in registers -- counted, ranked (the returning LDS atomic of the count IS the
         // rank) and written to its block's run. Inside a block the records are ordered by sub-cell of the block (SHACIRA_SORT_SUB
         // bits per axis; the key is block * cells + cell, block_start still addresses whole blocks): consecutive samples then
@@ -484,7 +541,7 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp,
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             const uint32_t p = lo + (uint32_t)u * kSortThreadsS + threadIdx.x;
-            r[u] = inter4[p < hi ? p : (hi > 0u ? hi - 1u : 0u)];
+            r[u] = fetch(p < hi ? p : (hi > lo ? hi - 1u : lo));
         }
 #pragma unroll
         for (int u = 0; u < R; ++u) {
@@ -497,28 +554,28 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp,
         // in registers already): wave scans + wave totals
         {
             constexpr int KPT = (kKeys + kSortThreadsS - 1) / kSortThreadsS;
-            uint32_t cnt[KPT], sum = 0;
+            uint32_t kc[KPT], sum = 0;
 #pragma unroll
             for (int q = 0; q < KPT; ++q) {
                 const uint32_t k = threadIdx.x * KPT + q;
-                cnt[q] = k < (uint32_t)kKeys ? s_tot8[k] : 0u;
-                sum += cnt[q];
+                kc[q] = k < (uint32_t)kKeys ? s_tot8[k] : 0u;
+                sum += kc[q];
             }
-            uint32_t incl = sum;
+            uint32_t kincl = sum;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t nbr = __shfl_up(incl, off, 64);
-                if (lane >= (uint32_t)off) incl += nbr;
+                const uint32_t nbr = __shfl_up(kincl, off, 64);
+                if (lane >= (uint32_t)off) kincl += nbr;
             }
-            if (lane == 63) s_wtot[threadIdx.x >> 6] = incl;
+            if (lane == 63) s_wtot[wave] = kincl;
             __syncthreads();
-            uint32_t run = incl - sum;
-            for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) run += s_wtot[w];
+            uint32_t run = kincl - sum;
+            for (uint32_t w = 0; w < wave; ++w) run += s_wtot[w];
 #pragma unroll
             for (int q = 0; q < KPT; ++q) {
                 const uint32_t k = threadIdx.x * KPT + q;
                 if (k < (uint32_t)kKeys) s_off8[k] = run;
-                run += cnt[q];
+                run += kc[q];
             }
         }
         __syncthreads();
@@ -529,21 +586,40 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp,
             if (lo + (uint32_t)u * kSortThreadsS + threadIdx.x < hi) sorted4[lo + s_off8[j[u]] + rk[u]] = r[u];
         return;
     }
-    // a chunk of an over-full bin (a batch concentrated in few blocks; the partition pass counted such bins' records per block):
-    // block offsets of the bin from the global counts, then the chunk's <= 8 192 records, held in registers, ranked inside the
+    // a chunk of an over-full bin (a batch concentrated in few blocks): block offsets of the bin from the first pass's counts
+    // per (tile, block), summed over the tiles; then the chunk's <= 8 192 records, held in registers, ranked inside the
     // workgroup with LDS atomics (a wave whose lanes all name one block draws once) and ONE global reservation per block of the
     // bin (per-lane returning atomics on <= 16 global words serialised: 0.7 ms for a Gaussian blob of 2^20 samples). Order inside
     // a block is arrival order: these bins keep block order only (no sub-cell order).
-    __shared__ uint32_t s_off[kBpc + 1], s_cnt[kBpc], s_base[kBpc];
+    __shared__ uint32_t s_off[kBpc + 1], s_btot[kBpc], s_cnt[kBpc], s_base[kBpc];
+    if (threadIdx.x < kBpc) {
+        s_btot[threadIdx.x] = 0u;
+        s_cnt[threadIdx.x] = 0u;
+    }
+    __syncthreads();
+    {
+        const uint32_t b = threadIdx.x & (kBpc - 1u);
+        const bool col = b < bpc && key0 + b < tp.num_blocks;
+        const uint32_t blk = col ? key0 + b : tp.num_blocks - 1u;
+        uint32_t sum = 0;
+        for (uint32_t t0 = 0; t0 < tp.ptiles; t0 += kSortThreadsS / kBpc) {   // (workgroup-uniform)
+            const uint32_t tl = t0 + threadIdx.x / kBpc;
+            const uint32_t v = bcnt_at(bcnt, tp, tl < tp.ptiles ? tl : tp.ptiles - 1u, blk);
+            sum += (col && tl < tp.ptiles) ? v : 0u;
+        }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        if (lane < (uint32_t)kBpc && sum) atomicAdd(&s_btot[b], sum);
+    }
+    __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t run = 0;
         for (uint32_t b = 0; b < bpc; ++b) {
             s_off[b] = run;
-            run += (key0 + b < tp.num_blocks) ? gcount[key0 + b] : 0u;
+            run += s_btot[b];
         }
         s_off[bpc] = run;
     }
-    if (threadIdx.x < kBpc) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     if (first) {
         if (threadIdx.x < bpc && key0 + threadIdx.x < tp.num_blocks) block_start[key0 + threadIdx.x] = lo + s_off[threadIdx.x];
@@ -554,7 +630,7 @@ __global__ __launch_bounds__(kSortThreadsS) void psort_local_kernel(TilePlan tp,
 #pragma unroll
     for (int u = 0; u < R; ++u) {
         const uint32_t p = c_lo + (uint32_t)u * kSortThreadsS + threadIdx.x;
-        r[u] = inter4[p < c_hi ? p : c_hi - 1u];
+        r[u] = fetch(p < c_hi ? p : c_hi - 1u);
     }
 #pragma unroll
     for (int u = 0; u < R; ++u) {
@@ -606,7 +682,7 @@ size_t sample_plan_bytes(int dim, int64_t n) {
 }
 size_t sample_plan_scratch_bytes(int dim, int64_t n) { return n > 0 ? scratch_bytes_of(dim, n) : 0; }
 
-// the sort: coordinates -> plan (sorted records + block offsets); three launches on `s`
+// the sort: coordinates -> plan (sorted records + block offsets); two launches on `s`
 hipError_t sample_plan_build(int dim, const float *coords, int64_t n, void *plan, void *scratch, hipStream_t s) {
     TilePlan tp;
     make_sort_plan(dim, n, tp);
@@ -615,14 +691,11 @@ hipError_t sample_plan_build(int dim, const float *coords, int64_t n, void *plan
     carve_scratch(dim, n, scratch, c);
     // workgroups of the last pass: one per coarse bin + one per 8 192-record window (the remainders of over-full bins)
     const uint32_t chunks = tp.num_coarse + (uint32_t)((n + kLocalCap - 1) / kLocalCap);
-    uint32_t *gcount = c.gcursor + kMaxBlocksS;
-#define SHACIRA_SORT_LAUNCHES(D)                                                                                          \
-    hipLaunchKernelGGL(psort_count_kernel<D>, dim3(tp.ptiles), dim3(kSortThreadsS), 0, s, tp, coords, n, c.cnt, c.gcursor);  \
-    SHACIRA_CHECK_LAUNCH();                                                                                                  \
-    hipLaunchKernelGGL(psort_partition_kernel<D>, dim3(tp.ptiles), dim3(kSortThreadsS), 0, s, tp, coords, n, c.cnt, c.cbase, \
-                       c.gcursor, c.inter4);                                                                                 \
-    SHACIRA_CHECK_LAUNCH();                                                                                                  \
-    hipLaunchKernelGGL(psort_local_kernel<D>, dim3(chunks), dim3(kSortThreadsS), 0, s, tp, c.inter4, c.cbase, gcount,        \
+#define SHACIRA_SORT_LAUNCHES(D)                                                                                            \
+    hipLaunchKernelGGL(psort_partition_kernel<D>, dim3(tp.ptiles), dim3(kSortThreadsS), 0, s, tp, coords, n, c.cnt, c.coff, c.bcnt, \
+                       c.gcursor, c.inter4);                                                                                   \
+    SHACIRA_CHECK_LAUNCH();                                                                                                    \
+    hipLaunchKernelGGL(psort_local_kernel<D>, dim3(chunks), dim3(kSortThreadsS), 0, s, tp, c.inter4, c.cnt, c.coff, c.bcnt,   \
                        c.gcursor, c.sorted4, c.block_start, c.header, (uint32_t)n);
     if (dim == 3) {
         SHACIRA_SORT_LAUNCHES(3)
@@ -657,9 +730,9 @@ void sample_plan_view(int dim, int64_t n, const void *plan, SortedBatch &out) {
 }
 
 // workspace of the cell-sorted forward: the fine levels' staging, the sort's scratch, and -- when the caller keeps no plan
-// buffer of its own -- the plan
-size_t tiled_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n) {
-    return staged_bytes(dtype, lt, n) + scratch_bytes_of(dim, n) + plan_bytes_of(n);
+// buffer of its own -- the plan (last, so that a caller's plan only shortens the workspace)
+size_t tiled_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n, bool caller_plan) {
+    return staged_bytes(dtype, lt, n) + scratch_bytes_of(dim, n) + (caller_plan ? 0 : plan_bytes_of(n));
 }
 
 hipError_t tiled_forward(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx, const float *coords,

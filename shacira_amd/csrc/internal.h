@@ -26,7 +26,8 @@ struct PerDeviceOnce {
 };
 
 // hashgrid_fwd.hip
-size_t hashgrid_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n);
+// `caller_plan`: the call brings a plan buffer of its own, so the workspace holds none
+size_t hashgrid_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n, bool caller_plan = false);
 hipError_t hashgrid_forward_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
                                      const float *coords, const void *table, void *feats, void *workspace, int64_t n,
                                      hipStream_t s, void *plan = nullptr, bool plan_ready = false);
@@ -39,7 +40,7 @@ hipError_t hashgrid_forward_rows(int dim, int dtype, const LevelTable &lt, const
                                  const void *table, const void *staged, void *feats, int64_t n, int lc, hipStream_t s);
 // hashgrid_tiled.hip: cell-sorted ("tiled") forward for large batches
 bool tiled_supported(int dim, int dtype, const LevelTable &lt, int64_t n);
-size_t tiled_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n);
+size_t tiled_forward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n, bool caller_plan = false);
 // `plan`: caller-owned plan buffer (sample_plan_bytes) the sort writes into, NULL = inside the workspace; `plan_ready`: it
 // already holds this batch's plan (the sort is skipped)
 hipError_t tiled_forward(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx, const float *coords,

@@ -220,6 +220,8 @@ def _hashgrid_forward(dim, coords, codebook, codebook_first_idx, resolution, cod
     L = _lib.lib()
     with _on_device(codebook.device):
         nbytes = _ws_bytes(0, dim, N, len(res), F, int(codebook_bitwidth), res, T, dt, _lib.options_epoch)
+        if plan is not None:   # the workspace query includes a plan region for calls that bring none (shacira_hip.h)
+            nbytes -= _ws_bytes(2, dim, N, len(res), F, int(codebook_bitwidth), res, T, dt, _lib.options_epoch)
         ws = _workspace(codebook.device, nbytes)
         if plan is None:
             rc = L.shacira_hashgrid_forward(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),

@@ -47,7 +47,7 @@ with open(os.path.join(out, f"{tag}_bench_rocprof_summary.md"), "w") as f:
             tf += per_step
         elif "shacira::" in r["Name"] or "fillBuffer" in r["Name"]:
             tb += per_step
-    f.write(f"\nforward operator = sample sort (psort_count + psort_partition + psort_local: the batch's plan) + "
+    f.write(f"\nforward operator = sample sort (psort_partition + psort_local: the batch's plan) + "
             f"hashgrid_fwd_level_pair (fine levels) + hashgrid_fwd_rows (coarse levels + row assembly) = {tf:.1f} us of kernel "
             f"time; backward operator (planned: sorted order) = zero_unowned_rows + front16<SORTED> (gradient rows gathered in plan "
             f"order, 16-byte transpose + bucket counts) + bin_scan_buckets + bin_scatter + bin_consume with brick_accumulate "

@@ -6,7 +6,7 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 # last occurrence of the sort's first kernel marks the last step
-first_kernel = sys.argv[2] if len(sys.argv) > 2 else 'psort_count'
+first_kernel = sys.argv[2] if len(sys.argv) > 2 else 'psort_partition'
 starts = [i for i, r in enumerate(rows) if first_kernel in r['Kernel_Name']]
 last = rows[starts[-2]:starts[-1]] if len(starts) > 1 else rows[starts[-1]:]
 t0 = int(last[0]['Start_Timestamp'])
