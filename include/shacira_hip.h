@@ -725,6 +725,58 @@ SHACIRA_API int shacira_raygen(const float *cams, int num_views, int width, int 
                                int bg_mode, float *origins, float *dirs, float *rgb, uint8_t *mask, void *stream);
 
 /*
+ * Pixel batches and the pixel loss: an image fit's coordinates, target colours, squared error and "clamped PSNR" statistics made
+ * from pixel indices and ONE uint8 image that stays on the device -- what wisp/datasets/formats/multi_image_dataset.py:140-161
+ * stores per pixel (40 bytes on the host) and :190-242 gathers per batch, and what wisp/ops/image/metrics.py:39-58 computes from a
+ * materialised fp32 target. Operands common to the three calls:
+ *   image          uint8 [height, width, 3], contiguous, on the device; height, width in 1 .. 2^31 - 1. Every byte offset is
+ *                  64-bit: an image of 2^31 bytes or more works
+ *   pixel_idx      int32 [n] (idx_bits == 32) or int64 [n] (idx_bits == 64), pixel p = y * width + x. NULL: the range form, pixel
+ *                  i is start + i, with 0 <= start and start + n <= height * width (start is ignored with indices)
+ *   n              rows; 0 returns 0 with nothing enqueued, whatever the pointers (sizes, idx_bits and strides are checked first)
+ * shacira_pixel_batch: coords fp32 [n, 2] and rgb fp32 [n, 3], dense; either may be NULL (not written), not both. fp32, one
+ * rounding per operator as written (correctly rounded divisions, no fused multiply-add), y = p / width and x = p - y * width in
+ * integers:
+ *     coords = (((float)y / (float)height - 0.5f) * 2.0f, ((float)x / (float)width - 0.5f) * 2.0f)        the ROW comes first
+ *     rgb[c] = (float)byte[c] / 255.0f
+ * the reference's lattice (multi_image_dataset.py:148-153) and torchvision's ToTensor. The integer split is exact for every image;
+ * the reference's transform_coords (:232-242) divides the index by an fp32 tensor and agrees with it only up to 2^24 pixels. An
+ * index outside [0, height * width) reads nothing and gets NaN in its rows; every other row is unaffected. No workspace, no
+ * atomics: capturable, two calls return the same bits.
+ * shacira_pixel_loss_forward: pred fp32 [n, >= 3] with pred_stride >= 3 floats between rows (only the first three columns are
+ * read), stats fp64 [3] on the device, overwritten. Per pixel and channel:
+ *     d        = pred - (float)byte / 255.0f               fp32, one rounding each, as torch computes pred - target
+ *     stats[0] += (double)d * (double)d                    a NaN or infinite prediction shows here
+ *     lvl      = (uint8)(min(max(pred, 0), 1) * 255.0f)    truncated; a NaN prediction gives level 0
+ *     stats[1] += (lvl - byte)^2                           integers: this sum is exact (the target's own level IS its byte)
+ *   stats[2] = the number of pixels that counted. An index out of range is skipped: its row of pred is not read and it is not
+ *   counted. out_image uint8 [height, width, 3] or NULL: the three levels are stored at the pixel's place, every other byte is
+ *   left alone. Duplicate indices in one call race on out_image (one of the duplicates' levels is kept); stats does not depend
+ *   on it. workspace: shacira_pixel_loss_workspace_bytes(n) bytes (0 for n <= 0): one partial of SHACIRA_PIXEL_PARTIAL_BYTES per
+ *   workgroup, at most SHACIRA_PIXEL_MAX_GRID of them. Each workgroup adds its pixels in a fixed order in fp64, a one-workgroup
+ *   finish kernel adds the partials in a fixed order: no floating-point atomics, two calls return the same bits.
+ * shacira_pixel_loss_backward: grad_pred fp32 [n, 3] dense, overwritten: grad_pred[i, c] = g * (2.0f * d) with g = grad[0] read
+ * from the device (no read-back) -- the single rounding per product of torch's backward of ((pred - target) ** 2).sum(), so the
+ * same bits. Skipped rows get 0.
+ * Validation precedes any HIP call: SHACIRA_EINVAL for height or width outside 1 .. 2^31 - 1, n < 0, idx_bits outside {32, 64}
+ * with indices, a range that leaves the image, pred_stride < 3 or n * pred_stride beyond 2^59, a NULL operand (image; coords and
+ * rgb both; pred, stats, grad, grad_pred), a missing or short workspace. Everything runs on `stream` without allocation or
+ * synchronisation.
+ */
+#define SHACIRA_PIXEL_MAX_GRID 2048
+#define SHACIRA_PIXEL_PARTIAL_BYTES 24
+SHACIRA_API int shacira_pixel_batch(const uint8_t *image, int64_t height, int64_t width, const void *pixel_idx, int idx_bits,
+                                    int64_t start, int64_t n, float *coords, float *rgb, void *stream);
+SHACIRA_API size_t shacira_pixel_loss_workspace_bytes(int64_t n);
+SHACIRA_API int shacira_pixel_loss_forward(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height,
+                                           int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n,
+                                           uint8_t *out_image, double *stats, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+SHACIRA_API int shacira_pixel_loss_backward(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height,
+                                            int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n,
+                                            const float *grad, float *grad_pred, void *stream);
+
+/*
  * Latent decode, deterministic (non-SGA) path of LatentDecoder.forward with num_layers_dec == 0
  * (basic_latent_decoder.py:192-198 with DecoderLayer.forward :86-91):
  *     q        = rint(latent)                       round-half-to-even, torch.round (StraightThrough :28-36)

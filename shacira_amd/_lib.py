@@ -24,6 +24,7 @@ OCTREE_MAX_LEVEL = 10                                         # SHACIRA_OCTREE_M
 SSIM_WINDOW, SSIM_TILE_H, SSIM_TILE_W = 11, 16, 64            # SHACIRA_SSIM_* of the header
 POSENC_MAX_DIM, POSENC_MAX_BANDS, POSENC_MAX_PREFIX = 4, 64, 1 << 30   # SHACIRA_POSENC_* of the header
 RAYGEN_RECORD_FLOATS, RAYGEN_BG_WHITE, RAYGEN_BG_BLACK = 20, 0, 1       # SHACIRA_RAYGEN_* of the header
+PIXEL_MAX_GRID, PIXEL_PARTIAL_BYTES = 2048, 24                          # SHACIRA_PIXEL_* of the header
 
 _lock = threading.Lock()
 _lib = None
@@ -76,6 +77,10 @@ SIGNATURES = {
     "shacira_posenc_backward2": (_i, [_i64, _i, _i, _i, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "shacira_raygen_record_floats": (_i, []),
     "shacira_raygen": (_i, [_p, _i, _i, _i, _p, _p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "shacira_pixel_batch": (_i, [_p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p]),
+    "shacira_pixel_loss_workspace_bytes": (_sz, [_i64]),
+    "shacira_pixel_loss_forward": (_i, [_p, _i64, _p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "shacira_pixel_loss_backward": (_i, [_p, _i64, _p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p]),
     "shacira_find_depth_bound":(_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),

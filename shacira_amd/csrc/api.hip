@@ -619,6 +619,49 @@ int shacira_raygen(const float *cams, int num_views, int width, int height, cons
                                 bg_mode == SHACIRA_RAYGEN_BG_BLACK, origins, dirs, rgb, mask, (hipStream_t)stream);
 }
 
+// ---- pixel batches and the pixel loss ------------------------------------------------------------------------------------------
+// the operands the three calls share: the image's size, the index form and the range
+static bool pixel_args_ok(int64_t height, int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n) {
+    if (height <= 0 || width <= 0 || height > INT32_MAX || width > INT32_MAX || n < 0) return false;
+    if (pixel_idx) return idx_bits == 32 || idx_bits == 64;
+    return start >= 0 && n <= height * width && start <= height * width - n;      // the range form
+}
+
+int shacira_pixel_batch(const uint8_t *image, int64_t height, int64_t width, const void *pixel_idx, int idx_bits, int64_t start,
+                        int64_t n, float *coords, float *rgb, void *stream) {
+    if (!pixel_args_ok(height, width, pixel_idx, idx_bits, start, n)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;                       // an empty batch may come with NULL operands
+    if (!image || (!coords && !rgb)) return SHACIRA_EINVAL;
+    return (int)pixel_batch_dispatch(image, height, width, pixel_idx, idx_bits, start, n, coords, rgb, (hipStream_t)stream);
+}
+
+size_t shacira_pixel_loss_workspace_bytes(int64_t n) { return pixel_loss_workspace(n); }
+
+static bool pixel_pred_ok(int64_t n, int64_t pred_stride) {       // byte offsets stay inside int64
+    return pred_stride >= 3 && pred_stride <= INT64_MAX / 16 / (n > 0 ? n : 1);
+}
+
+int shacira_pixel_loss_forward(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height, int64_t width,
+                               const void *pixel_idx, int idx_bits, int64_t start, int64_t n, uint8_t *out_image, double *stats,
+                               void *workspace, size_t workspace_bytes, void *stream) {
+    if (!pixel_args_ok(height, width, pixel_idx, idx_bits, start, n) || !pixel_pred_ok(n, pred_stride)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;
+    if (!pred || !image || !stats) return SHACIRA_EINVAL;
+    if (!workspace || workspace_bytes < pixel_loss_workspace(n)) return SHACIRA_EINVAL;
+    return (int)pixel_loss_forward_dispatch(pred, pred_stride, image, height, width, pixel_idx, idx_bits, start, n, out_image,
+                                            stats, workspace, (hipStream_t)stream);
+}
+
+int shacira_pixel_loss_backward(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height, int64_t width,
+                                const void *pixel_idx, int idx_bits, int64_t start, int64_t n, const float *grad,
+                                float *grad_pred, void *stream) {
+    if (!pixel_args_ok(height, width, pixel_idx, idx_bits, start, n) || !pixel_pred_ok(n, pred_stride)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;
+    if (!pred || !image || !grad || !grad_pred) return SHACIRA_EINVAL;
+    return (int)pixel_loss_backward_dispatch(pred, pred_stride, image, height, width, pixel_idx, idx_bits, start, n, grad,
+                                             grad_pred, (hipStream_t)stream);
+}
+
 // ---- positional-encoding rows ----------------------------------------------------------------------------------------------
 // the shape shared by the three calls; `width` = P + E. Row strides are checked by the callers
 static bool posenc_shape_ok(int64_t n, int d, int num_bands, int64_t prefix_width, int64_t *width) {

@@ -180,6 +180,18 @@ hipError_t raygen_dispatch(const float *cams, int num_views, int width, int heig
                            const int32_t *pixel_idx, const float *jitter, int64_t n, const uint8_t *images, int channels,
                            bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s);
 
+// pixels.hip: coordinates and colours of pixels of one uint8 [H, W, 3] image, and the squared-error loss of predictions against
+// them (arguments checked by the entry points; pixel_idx == NULL is the range form, pixel i = start + i)
+size_t pixel_loss_workspace(int64_t n);
+hipError_t pixel_batch_dispatch(const uint8_t *image, int64_t height, int64_t width, const void *pixel_idx, int idx_bits,
+                                int64_t start, int64_t n, float *coords, float *rgb, hipStream_t s);
+hipError_t pixel_loss_forward_dispatch(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height,
+                                       int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n,
+                                       uint8_t *out_image, double *stats, void *workspace, hipStream_t s);
+hipError_t pixel_loss_backward_dispatch(const float *pred, int64_t pred_stride, const uint8_t *image, int64_t height,
+                                        int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n,
+                                        const float *grad, float *grad_pred, hipStream_t s);
+
 // sphere_trace.hip: find_depth_bound and the fused sphere-trace step (0 < P <= K < 2^31, checked by the entry points)
 hipError_t find_depth_bound_launch(int64_t P, int64_t K, const float *query, const int32_t *curr, const int32_t *pack_end,
                                    const float *depth, int32_t *out, hipStream_t s);

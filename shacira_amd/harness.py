@@ -349,6 +349,159 @@ def fit_image(device, steps=1000, height=512, width=768, seed=0, num_lods=16, lo
                 file_bytes=file_bytes, steps=steps, history=history, ms_per_step=t_loop / steps * 1e3)
 
 
+def pixel_loss(pred, dataset, pixel_idx=None, start=0, out_image=None):
+    """(sq_sum, stats) of ``pred`` against pixels of the dataset's resident uint8 image: ``hip_ops.pixel_loss`` (one fused pass
+    over the image's bytes) on the device; on a host dataset the same definitions in torch ops."""
+    image = dataset.image
+    if image.is_cuda:
+        from . import hip_ops
+        return hip_ops.pixel_loss(pred, image, pixel_idx, start, out_image)
+    flat = image.reshape(-1, 3)
+    if pixel_idx is None:
+        pixel_idx = torch.arange(start, start + pred.shape[0], dtype=torch.int64)
+    p = pixel_idx.reshape(-1).to(torch.int64)
+    ok = (p >= 0) & (p < flat.shape[0])
+    p, rows = p[ok], pred[:, :3][ok]
+    bytes_ = flat[p]
+    d = rows - bytes_.to(torch.float32) / 255.0
+    sq_sum = (d ** 2).sum()
+    with torch.no_grad():
+        lvl = (torch.nan_to_num(torch.clamp(rows, 0, 1), nan=0.0) * 255).to(torch.uint8)
+        if out_image is not None:
+            out_image.reshape(-1, 3)[p] = lvl
+        stats = torch.stack([(d.double() ** 2).sum(), ((lvl.double() - bytes_.double()) ** 2).sum(),
+                             torch.tensor(float(p.shape[0]), dtype=torch.float64)])
+    return sq_sum, stats
+
+
+class DatasetImageFitter(ImageFitter):
+    """The step of ``ImageFitter`` fed by a ``MultiImageDataset``: every step takes the dataset's next batch (``dataset.batch``;
+    uniform draws in 'wreplace' mode) and forms the loss AND the logged clamped-PSNR statistics with ``pixel_loss`` from the
+    resident uint8 image. No fp32 target is kept and no quantisation chain runs; the statistics are three doubles on the device
+    until ``read_last`` fetches them. Single rank."""
+
+    def __init__(self, nef, dataset, total_steps, cdec, cent, **kw):
+        first = dataset.batch(0)
+        super().__init__(nef, first["coords"], None, total_steps, cdec, cent, **kw)
+        assert self.world == 1, "DatasetImageFitter: single-rank path"
+        self.dataset = dataset
+        self._next = 0
+
+    def _batch(self):
+        ds = self.dataset
+        if self._next >= len(ds):          # an epoch of the current image is over
+            ds.resample()
+            self._next = 0
+        b = ds.batch(self._next)
+        self._next += 1
+        return b
+
+    def step(self, read=True):
+        self.iteration += 1
+        self.optimizer.zero_grad(set_to_none=True)
+        with torch.no_grad():
+            self._update_div()
+        if self.temperature_sched is not None:
+            dec = self.nef.grid.latent_dec
+            dec.temperature = self.temperature_sched(self.iteration)
+            if self.iteration / self.total_steps > self.cdec["decay_period"]:
+                dec.use_sga = False
+        b = self._batch()
+        pred = self.nef.rgb(b["coords"])
+        if isinstance(pred, dict):
+            pred = pred["rgb"]
+        sq_sum, stats = pixel_loss(pred, self.dataset, b["pixel_idx"], b["start"])
+        loss = sq_sum / (pred.shape[0] * 3)
+        lam = self.lambda_sched(self.iteration - 1)
+        avg_bits = torch.zeros(())
+        if self.cdec["ldecode_enabled"] and lam > 0:
+            avg_bits, _ = self.nef.grid.ent_loss(self.iteration - 1, is_val=not self.nef.training)
+            loss = loss + lam * avg_bits
+        loss.backward()
+        self.optimizer.step()
+        self._last = (stats, avg_bits.detach() if torch.is_tensor(avg_bits) else avg_bits)
+        return self.read_last() if read else None
+
+    def read_last(self):
+        """(rgb_loss, clamped PSNR, avg bits) of the last step: one read-back of the three statistics."""
+        stats, avg_bits = self._last
+        st = stats.tolist()
+        n = max(st[2], 1.0) * 3
+        return st[0] / n, 20 * math.log10(255.0) - 10 * math.log10(max(st[1] / n, 1e-12)), float(avg_bits)
+
+
+def fit_image_dataset(dataset, device, steps=1000, seed=0, num_lods=16, log_every=0, hidden_dim=16, use_sga=False):
+    """Fit the dataset's current image (the first one is loaded if none is) with the config-B LatentGrid, the step of
+    ``fit_image`` fed by ``dataset.batch`` / ``dataset.sample`` and scored by ``pixel_loss``. Returns dict(nef, psnr, rgb_loss,
+    avg_bits, losses [steps] on the host, history, ms_per_step); ``losses`` is read back once, after the loop."""
+    import time
+    torch.manual_seed(seed)
+    if dataset.image is None:
+        dataset.load_next()
+    grid, cdec, cent = kodak_like_grid(num_lods=num_lods, use_sga=use_sga)
+    nef = NeuralImage(grid, hidden_dim=hidden_dim, num_layers=1).to(device)
+    fitter = DatasetImageFitter(nef, dataset, steps, cdec, cent)
+    history, kept, out = [], [], None
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t_loop = time.perf_counter()
+    for it in range(steps):
+        want = (log_every and (it + 1) % log_every == 0) or it == steps - 1
+        out = fitter.step(read=bool(want))
+        kept.append(fitter._last[0])
+        if log_every and (it + 1) % log_every == 0:
+            history.append((it + 1,) + out)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t_loop = time.perf_counter() - t_loop
+    st = torch.stack(kept).cpu()
+    losses = (st[:, 0] / (st[:, 2].clamp(min=1.0) * 3)).tolist()
+    return dict(nef=nef, psnr=out[1], rgb_loss=out[0], avg_bits=out[2], losses=losses, steps=steps, history=history,
+                ms_per_step=t_loop / steps * 1e3)
+
+
+def validate_image(nef, dataset, chunk=65536):
+    """The reference's ``ImageTrainer.validate`` (wisp/trainers/image_trainer.py:377-432) on the dataset's current image: the
+    pixels are walked in image ('eval') order in chunks of ``chunk``, each chunk's coordinates come from the pixel kernel, and
+    ONE ``pixel_loss`` call per chunk adds the chunk's statistics and stores its predictions' 8-bit levels at their places of
+    ``pred``. SGA sampling is off and the model in eval mode for the walk, as in the reference. Returns {"psnr": the clamped
+    PSNR of the whole image, "mse": the mean squared error per element, "clamped_mse": in levels squared per element, "pred":
+    uint8 [H, W, 3] on the dataset's device}; one read-back, at the end. (The reference divides its summed error by the number
+    of pixels, not elements, and averages per-chunk PSNRs by pixel count; the whole-image definitions of
+    ``wisp.ops.image.metrics`` are used instead, so ``psnr`` and ``clamped_mse`` are the numbers ``metrics.clamped_psnr`` and
+    ``metrics.clamped_mse`` report for the same predictions.)"""
+    H, W = dataset.image_size
+    pred_image = torch.zeros((H, W, 3), dtype=torch.uint8, device=dataset.image.device)
+    total = torch.zeros(3, dtype=torch.float64, device=dataset.image.device)
+    dec = getattr(getattr(nef, "grid", None), "latent_dec", None)
+    sga_state = getattr(dec, "use_sga", None)
+    was_training = nef.training
+    if sga_state:
+        dec.use_sga = False
+    nef.eval()
+    try:
+        with torch.no_grad():
+            for start in range(0, H * W, chunk):
+                n = min(chunk, H * W - start)
+                coords, _ = dataset.pixels_of(None, start, n, want_rgb=False)
+                pred = nef.rgb(coords)
+                if isinstance(pred, dict):
+                    pred = pred["rgb"]
+                _, stats = pixel_loss(pred, dataset, None, start, pred_image)
+                total += stats
+    finally:
+        nef.train(was_training)
+        if sga_state:
+            dec.use_sga = sga_state
+    st = total.tolist()
+    n = max(st[2], 1.0) * 3
+    # the mean of the level errors as metrics.clamped_mse / clamped_psnr form it: an fp32 quotient of the (here exact) integer
+    # sum. The two paths then report the same number -- to the last bit while the sum is below 2^24, where fp32 adds exactly
+    clamped_mse = float(np.float32(st[1]) / np.float32(n))
+    return {"psnr": 20 * math.log10(255.0) - 10 * math.log10(max(clamped_mse, 1e-12)), "mse": st[0] / n,
+            "clamped_mse": clamped_mse, "pred": pred_image}
+
+
 # =====================================================================================================================
 # 3-D: NeRF-like ray points against an analytic field (configs D / E of SURVEY.md section 8)
 # =====================================================================================================================

@@ -1304,3 +1304,129 @@ def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, i
                                        _ptr(origins), _ptr(dirs), _ptr(rgb), _ptr(mask), _stream(records))
     _lib.check(rc, "raygen")
     return origins, dirs, rgb, mask
+
+
+# ---- pixel batches and the pixel loss (include/shacira_hip.h, shacira_pixel_batch / shacira_pixel_loss_*) -----------------------
+def _pixel_operands(image, pixel_idx, start, n, what):
+    """The checked operands the pixel calls share: (image, H, W, pixel_idx, idx_bits, start, n)."""
+    _need_gpu(image, pixel_idx)
+    dev = image.device
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_contiguous():
+        raise RuntimeError(f"shacira_amd: {what} expects a contiguous uint8 image [H, W, 3], got {image.dtype} "
+                           f"{tuple(image.shape)}")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if H < 1 or W < 1:
+        raise RuntimeError(f"shacira_amd: {what} expects an image of at least one pixel, got {H} x {W}")
+    if pixel_idx is None:
+        start = int(start)
+        n = H * W - start if n is None else int(n)
+        if start < 0 or n < 0 or start + n > H * W:
+            raise RuntimeError(f"shacira_amd: {what}: pixels {start} .. {start + n} are not inside a {H} x {W} image")
+        return image, H, W, None, 64, start, n
+    if pixel_idx.dtype not in (torch.int32, torch.int64) or pixel_idx.device != dev:
+        raise RuntimeError(f"shacira_amd: {what} expects int32 or int64 pixel_idx on {dev}, got {pixel_idx.dtype} on "
+                           f"{pixel_idx.device}")
+    if pixel_idx.dim() == 2 and pixel_idx.shape[1] == 1:       # the [n, 1] indices the 'eval' and 'wreplace' batches carry
+        pixel_idx = pixel_idx.reshape(-1)
+    if pixel_idx.dim() != 1 or (n is not None and int(n) != pixel_idx.shape[0]):
+        raise RuntimeError(f"shacira_amd: {what} expects pixel_idx [n] or [n, 1], got {tuple(pixel_idx.shape)}"
+                           + (f" for n = {n}" if n is not None else ""))
+    pixel_idx = pixel_idx.contiguous()
+    return image, H, W, pixel_idx, 32 if pixel_idx.dtype == torch.int32 else 64, 0, pixel_idx.shape[0]
+
+
+def pixel_batch(image, pixel_idx=None, start=0, n=None, want_coords=True, want_rgb=True):
+    """(coords, rgb) of pixels of ``image`` (uint8 [H, W, 3] on the device) in one kernel: fp32 [n, 2] in [-1, 1) with the ROW
+    first and fp32 [n, 3] = byte / 255; the one not wanted is None. ``pixel_idx``: int32 or int64 [n] (or [n, 1]), pixel =
+    y * W + x; None: the range form, pixels ``start .. start + n`` (default: to the end of the image). An index out of range
+    gives NaN rows. Not differentiable."""
+    image, H, W, pixel_idx, bits, start, n = _pixel_operands(image, pixel_idx, start, n, "pixel_batch")
+    if not (want_coords or want_rgb):
+        raise RuntimeError("shacira_amd: pixel_batch makes coords, rgb or both")
+    dev = image.device
+    coords = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_coords else None
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_rgb else None
+    if n == 0:
+        return coords, rgb
+    with _on_device(dev):
+        rc = _lib.lib().shacira_pixel_batch(_ptr(image), H, W, _ptr(pixel_idx), bits, start, n, _ptr(coords), _ptr(rgb),
+                                            _stream(image))
+    _lib.check(rc, "pixel_batch")
+    return coords, rgb
+
+
+def _pixel_pred(pred, n, dev):
+    """``pred`` as the fp32 [n, 3+] device operand of the loss kernels and its row stride in floats (a row-strided view such as
+    ``x[:, :3]`` goes through as it is)."""
+    _need_gpu(pred)
+    if pred.dtype != torch.float32 or pred.dim() != 2 or pred.shape[0] != n or pred.shape[1] < 3 or pred.device != dev:
+        raise RuntimeError(f"shacira_amd: pixel_loss expects fp32 pred [{n}, 3+] on {dev}, got {pred.dtype} "
+                           f"{tuple(pred.shape)} on {pred.device}")
+    pred = pred.detach()
+    if pred.stride(1) != 1 or (n > 1 and pred.stride(0) < pred.shape[1]):
+        pred = pred.contiguous()
+    return pred, (pred.stride(0) if n > 1 else max(int(pred.shape[1]), 3))
+
+
+@functools.lru_cache(maxsize=256)
+def _pixel_loss_ws_bytes(n):
+    return int(_lib.lib().shacira_pixel_loss_workspace_bytes(n))
+
+
+class _PixelLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, image, pixel_idx, start, out_image):
+        image, H, W, pixel_idx, bits, start, n = _pixel_operands(image, pixel_idx, start,
+                                                                 pred.shape[0] if pred.dim() == 2 else None, "pixel_loss")
+        dev = image.device
+        p, ps = _pixel_pred(pred, n, dev)
+        if out_image is not None and (out_image.dtype != torch.uint8 or tuple(out_image.shape) != (H, W, 3)
+                                      or out_image.device != dev or not out_image.is_contiguous()):
+            raise RuntimeError(f"shacira_amd: pixel_loss out_image must be contiguous uint8 [{H}, {W}, 3] on {dev}")
+        # the finish kernel overwrites all three: zeros only where nothing is enqueued
+        stats = (torch.empty if n > 0 else torch.zeros)(3, dtype=torch.float64, device=dev)
+        if n > 0:
+            L = _lib.lib()
+            with _on_device(dev):
+                nbytes = _pixel_loss_ws_bytes(n)
+                ws = _workspace(dev, nbytes)
+                rc = L.shacira_pixel_loss_forward(_ptr(p), ps, _ptr(image), H, W, _ptr(pixel_idx), bits, start, n,
+                                                  _ptr(out_image), _ptr(stats), _ptr(ws), nbytes, _stream(image))
+            _lib.check(rc, "pixel_loss_forward")
+        ctx.save_for_backward(p, image, pixel_idx)
+        ctx.geom = (ps, H, W, bits, start, n, tuple(pred.shape))
+        ctx.mark_non_differentiable(stats)
+        return stats[0].to(torch.float32), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sq, _grad_stats):
+        p, image, pixel_idx = ctx.saved_tensors
+        ps, H, W, bits, start, n, shape = ctx.geom
+        dev = image.device
+        # columns beyond the third are not read: their gradient is zero
+        grad = (torch.zeros if shape[1] > 3 else torch.empty)(shape, dtype=torch.float32, device=dev)
+        if n == 0:
+            return grad, None, None, None, None
+        g = grad_sq.detach().to(dtype=torch.float32).reshape(1).contiguous()
+        rows = grad if shape[1] == 3 else torch.empty((n, 3), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            rc = _lib.lib().shacira_pixel_loss_backward(_ptr(p), ps, _ptr(image), H, W, _ptr(pixel_idx), bits, start, n, _ptr(g),
+                                                        _ptr(rows), _stream(image))
+        _lib.check(rc, "pixel_loss_backward")
+        if rows is not grad:
+            grad[:, :3] = rows
+        return grad, None, None, None, None
+
+
+def pixel_loss(pred, image, pixel_idx=None, start=0, out_image=None):
+    """(sq_sum, stats) of predictions ``pred`` (fp32 [n, 3+], the first three columns) against pixels of ``image`` (uint8
+    [H, W, 3]) in one pass over the image's bytes: ``sq_sum`` fp32 0-dim = sum (pred - byte / 255)^2, differentiable in ``pred``
+    (once: double backward raises); ``stats`` fp64 [3] = that sum in fp64, the exact sum of squared 8-bit level differences
+    (``metrics.clamped_mse`` times the element count) and the number of pixels that counted; not differentiable. ``pixel_idx``:
+    int32 or int64 [n] or [n, 1]; None: pixels ``start .. start + n``. ``out_image``: uint8 [H, W, 3] that receives the
+    predictions' levels at the pixels' places (duplicate indices race there, not in ``stats``). Indices out of range are skipped
+    and get a zero gradient. Nothing is read back: capturable, and deterministic to the bit."""
+    if pixel_idx is not None:
+        pixel_idx = pixel_idx.detach()
+    return _PixelLoss.apply(pred, image, pixel_idx, int(start), out_image)

@@ -1,3 +1,4 @@
-"""Datasets: multiview images and cameras kept on the device, rays made on demand by the fused ray kernel."""
+"""Datasets: images and cameras kept on the device as bytes; rays, coordinates and colours made on demand by fused kernels."""
 from .multiview_dataset import NeRFSyntheticDataset  # noqa: F401
+from .image_dataset import MultiImageDataset  # noqa: F401
 from .ray_sampler import SampleRays  # noqa: F401
