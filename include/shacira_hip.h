@@ -566,6 +566,91 @@ SHACIRA_API int shacira_mesh_voxelize(int64_t num_triangles, const float *triang
                                       size_t workspace_bytes, void *stream);
 
 /*
+ * Mesh point sampling (ABI 11, additive): training points on a mesh, near it, in the cube or inside octree cells, every one
+ * a pure function of (seed, sample index), optionally only those inside the occupied cells of one octree level. The
+ * reference samples with a chain of host-side torch calls on the global generator (wisp.ops.mesh sample_surface,
+ * sample_near_surface, sample_uniform and wisp.ops.spc sample_spc) and filters with cat, query and a boolean
+ * index (wisp/datasets/formats/octree_sdf_dataset.py); here one device function, make_sample(i), serves a counting and a
+ * writing kernel. tests/mesh_sample_ref.py restates it in numpy.
+ *
+ *   mode             SHACIRA_MESH_SAMPLE_SURFACE / NEAR / CUBE / CELLS
+ *   n                samples, local indices i = 0 .. n - 1
+ *   index_base       >= 0; the counter of sample i is idx = index_base + i (int64)
+ *   seed, segment    the Philox key and the fourth counter word (the datasets: the technique's position in sample_mode)
+ *   words            may be NULL. uint32 [n, 8]: row i replaces the eight Philox words of sample i (words 0..3 draw 0,
+ *                    4..7 draw 1), e.g. a low-discrepancy sequence. seed, segment and index_base are then not used
+ *   num_triangles T, triangles [T, 3, 3] fp32 (the layout of shacira_mesh_sdf), cdf uint32 [T]    SURFACE and NEAR: T >= 1
+ *   sigma            NEAR: the displacement's standard deviation (the reference's misnamed `variance`)
+ *   num_cells C, corners int16 [C, 3] (the layout of OctreeAS.points), samples_per_cell >= 1, cell_level    CELLS only:
+ *                    n must equal C * samples_per_cell, 0 <= cell_level <= SHACIRA_OCTREE_MAX_LEVEL
+ *   occupancy_words  may be NULL (no filter). uint32 [ceil(G^3 / 32)], G = 2^occupancy_level, 0 <= occupancy_level <=
+ *                    SHACIRA_OCTREE_MAX_LEVEL: bit (key & 31) of word (key >> 5), key = (x * G + y) * G + z -- what
+ *                    shacira_mesh_voxelize writes and OctreeAS.packed_occupancy returns
+ * Operands of other modes are not read and may be NULL.
+ *
+ * Random words: Philox4x32-10 (Salmon et al. 2011; multipliers D2511F53, CD9E8D57, key increments 9E3779B9, BB67AE85).
+ *   key = (seed low word, seed high word);  counter = (idx low word, idx high word, draw, segment)
+ *   draw 0 gives w0..w3 (the face and barycentric words, or the three coordinates of CUBE and CELLS; w3 is unused),
+ *   draw 1 gives g0..g3 (the Gaussian words; evaluated by NEAR only).
+ *   U(w) = (float)(w >> 8) * 2^-24 in [0, 1);   U1(w) = (float)((w >> 8) + 1) * 2^-24 in (0, 1]   (both exact)
+ * Face of a word (SURFACE, NEAR): cdf is the inclusive integer CDF of the face areas, non-decreasing, cdf[T - 1] > 0
+ *   (shacira_amd.hip_ops.mesh_face_cdf: a, b, c fp32; x = a - b, y = b - c in fp32; cross(x, y), its squares and their sum
+ *   ((nx^2 + ny^2) + nz^2), the square root and the running sum in fp64, in index order;
+ *   cdf[t] = min(floor(sum[t] / sum[T - 1] * 2^32), 2^32 - 1)). The rule, integers only:
+ *       w' = min(w0, cdf[T - 1] - 1);   face = the FIRST t with cdf[t] > w'   (a binary search for the upper bound)
+ *   Face t thus owns the words [cdf[t - 1], cdf[t]) (cdf[-1] = 0) and the last face of positive width also those from
+ *   cdf[T - 1] up. So: a face of zero area (cdf[t] == cdf[t - 1]; first: cdf[0] == 0) owns no word, wherever it stands;
+ *   every word has a face, since cdf[T - 1] > w'; and the share of a face differs from its area share by less than 2^-32 from
+ *   the floors at its two ends (no word is lost to the clamp). A cdf that breaks the preconditions reads nothing out of
+ *   bounds: the search never leaves [0, T - 1].
+ * Points, fp32, no contraction, one rounding per operator, cross(x, y) as in the shacira_mesh_sdf contract:
+ *   SURFACE  u = sqrtf(U(w1)), v = U(w2);  p = ((1 - u) * a + (u * (1 - v)) * b) + (u * v) * c  per coordinate;
+ *            normal = cross(a - b, b - c), not normalised;  face index = t
+ *   NEAR     the SURFACE point of (w0, w1, w2), then p_k = p_k + sigma * n_k with Box-Muller normals:
+ *            r = sqrtf(-2 * logf(U1(g0))), r' = sqrtf(-2 * logf(U1(g2)));  (s, c) = sincospif(2 * U(g1)), c' = cospi(2 * U(g3))
+ *            (the arguments are exact);  n = (r * c, r * s, r' * c').  sigma == 0 gives the SURFACE point. logf and
+ *            sincospif are the device library's: tests/test_gpu_mesh_sample.py bounds them against fp64
+ *   CUBE     p_k = U(w_k) * 2 - 1
+ *   CELLS    cell = i / samples_per_cell, c = corners[cell], W = 2 / 2^cell_level:  p_k = (c_k * W - 1) + U(w_k) * W
+ *            normal = 0 and face index = -1 for CUBE and CELLS
+ * Filter (occupancy_words != NULL): a sample is kept iff OctreeAS.query gives pidx > -1 at that level:
+ *   q_k = floorf((G * (p_k + 1)) / 2) in fp32;  kept iff 0 <= q_k < G for every k (false for NaN) and the bit of key(q) is set.
+ *
+ * shacira_mesh_sample_count: occupancy_words required. block_counts int32 [ceil(n / SHACIRA_MESH_SAMPLE_BLOCK)]: how many of
+ *   the block's consecutive indices are kept. One launch, no host synchronisation.
+ * shacira_mesh_sample: points fp32 [rows, 3]; normals fp32 [rows, 3], face_idx int32 [rows], source_idx int64 [rows] (the
+ *   local index i) may each be NULL.
+ *   block_offsets == NULL (occupancy_words must be NULL too): rows = n, sample i goes to row i.
+ *   block_offsets int64 [ceil(n / 256)], the exclusive scan of block_counts (occupancy_words required): the kept samples of
+ *   block b go to rows block_offsets[b] + rank, the rank counted in index order among the kept samples of the block (wavefront
+ *   ballot plus a four-entry LDS prefix): the output is the kept subsequence, in order. The samples are made again from their
+ *   indices, so no intermediate array exists and the two launches cannot disagree.
+ * One thread per sample, workgroups of 256, no scratch, no workspace, no allocation; all stores are ordinary vector stores.
+ *
+ * Bounds: 0 <= n, T, C < 2^31; index_base + n does not overflow int64. Address arithmetic is 64-bit. Validation happens
+ * before any HIP call: an unknown mode, bad counts or levels, n != C * samples_per_cell, and NULL operands of the mode return
+ * SHACIRA_EINVAL; n == 0 returns 0 and launches nothing. Each call is ONE launch on `stream` with no host synchronisation:
+ * safe to capture into a graph. The filtered form as a whole (count, scan, read the total to size the outputs, write) is
+ * not capturable: the caller reads the total back between the two calls.
+ */
+#define SHACIRA_MESH_SAMPLE_SURFACE 0
+#define SHACIRA_MESH_SAMPLE_NEAR 1
+#define SHACIRA_MESH_SAMPLE_CUBE 2
+#define SHACIRA_MESH_SAMPLE_CELLS 3
+#define SHACIRA_MESH_SAMPLE_BLOCK 256
+SHACIRA_API int shacira_mesh_sample_count(int mode, int64_t n, int64_t index_base, uint64_t seed, uint32_t segment,
+                                          const uint32_t *words, int64_t num_triangles, const float *triangles,
+                                          const uint32_t *cdf, float sigma, int64_t num_cells, const int16_t *corners,
+                                          int samples_per_cell, int cell_level, const uint32_t *occupancy_words,
+                                          int occupancy_level, int32_t *block_counts, void *stream);
+SHACIRA_API int shacira_mesh_sample(int mode, int64_t n, int64_t index_base, uint64_t seed, uint32_t segment,
+                                    const uint32_t *words, int64_t num_triangles, const float *triangles,
+                                    const uint32_t *cdf, float sigma, int64_t num_cells, const int16_t *corners,
+                                    int samples_per_cell, int cell_level, const uint32_t *occupancy_words,
+                                    int occupancy_level, const int64_t *block_offsets, float *points, float *normals,
+                                    int32_t *face_idx, int64_t *source_idx, void *stream);
+
+/*
  * Structural similarity (SSIM) of a prediction x against a target y, and its gradient with respect to x: what
  * skimage.metrics.structural_similarity(x, y, data_range=R, gaussian_weights=True, sigma=1.5, channel_axis=2) computes, the
  * second number the reference reports per validation image (wisp/ops/image/metrics.py:111-132).

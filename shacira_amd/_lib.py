@@ -25,6 +25,8 @@ SSIM_WINDOW, SSIM_TILE_H, SSIM_TILE_W = 11, 16, 64            # SHACIRA_SSIM_* o
 POSENC_MAX_DIM, POSENC_MAX_BANDS, POSENC_MAX_PREFIX = 4, 64, 1 << 30   # SHACIRA_POSENC_* of the header
 RAYGEN_RECORD_FLOATS, RAYGEN_BG_WHITE, RAYGEN_BG_BLACK = 20, 0, 1       # SHACIRA_RAYGEN_* of the header
 PIXEL_MAX_GRID, PIXEL_PARTIAL_BYTES = 2048, 24                          # SHACIRA_PIXEL_* of the header
+MESH_SAMPLE_SURFACE, MESH_SAMPLE_NEAR, MESH_SAMPLE_CUBE, MESH_SAMPLE_CELLS = 0, 1, 2, 3   # SHACIRA_MESH_SAMPLE_* of the header
+MESH_SAMPLE_BLOCK = 256
 
 _lock = threading.Lock()
 _lib = None
@@ -69,6 +71,10 @@ SIGNATURES = {
     "shacira_mesh_closest": (_i, [_i64, _i64, _p, _p, ctypes.c_int32, _p, _p, _p, _p, _sz, _p]),
     "shacira_mesh_voxelize_workspace_bytes": (_sz, [_i64, _i]),
     "shacira_mesh_voxelize": (_i, [_i64, _p, _i, _f, _p, _p, _p, _sz, _p]),
+    "shacira_mesh_sample_count": (_i, [_i, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32, _p, _i64, _p, _p, _f, _i64, _p, _i, _i, _p,
+                                       _i, _p, _p]),
+    "shacira_mesh_sample": (_i, [_i, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32, _p, _i64, _p, _p, _f, _i64, _p, _i, _i, _p, _i,
+                                 _p, _p, _p, _p, _p, _p]),
     "shacira_ssim_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
     "shacira_ssim_forward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),
     "shacira_ssim_backward": (_i, [_i64, _i64, _i, _i, _p, _p, _f, _p, _p, _p, _sz, _p]),

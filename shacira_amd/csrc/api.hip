@@ -565,6 +565,69 @@ int shacira_mesh_voxelize(int64_t num_triangles, const float *triangles, int lev
                                        (hipStream_t)stream);
 }
 
+// ---- mesh point sampling ---------------------------------------------------------------------------------------------------
+// 0: launch; 1: nothing to do (n == 0); SHACIRA_EINVAL
+static int mesh_sample_args(int mode, int64_t n, int64_t index_base, uint64_t seed, uint32_t segment, const uint32_t *words,
+                            int64_t num_triangles, const float *triangles, const uint32_t *cdf, float sigma,
+                            int64_t num_cells, const int16_t *corners, int samples_per_cell, int cell_level,
+                            const uint32_t *occupancy_words, int occupancy_level, MeshSampleArgs &a) {
+    if (mode < SHACIRA_MESH_SAMPLE_SURFACE || mode > SHACIRA_MESH_SAMPLE_CELLS) return SHACIRA_EINVAL;
+    if (n < 0 || n > INT32_MAX || index_base < 0 || index_base > INT64_MAX - n) return SHACIRA_EINVAL;
+    const bool faces = mode == SHACIRA_MESH_SAMPLE_SURFACE || mode == SHACIRA_MESH_SAMPLE_NEAR;
+    if (faces && (num_triangles < 0 || num_triangles > INT32_MAX)) return SHACIRA_EINVAL;
+    if (mode == SHACIRA_MESH_SAMPLE_CELLS) {
+        if (num_cells < 0 || num_cells > INT32_MAX || samples_per_cell < 1) return SHACIRA_EINVAL;
+        if (cell_level < 0 || cell_level > SHACIRA_OCTREE_MAX_LEVEL) return SHACIRA_EINVAL;
+        if (num_cells * (int64_t)samples_per_cell != n) return SHACIRA_EINVAL;
+    }
+    if (occupancy_words && (occupancy_level < 0 || occupancy_level > SHACIRA_OCTREE_MAX_LEVEL)) return SHACIRA_EINVAL;
+    if (n == 0) return 1;
+    if (faces && (num_triangles < 1 || !triangles || !cdf)) return SHACIRA_EINVAL;
+    if (mode == SHACIRA_MESH_SAMPLE_CELLS && !corners) return SHACIRA_EINVAL;
+    a.mode = mode;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.segment = segment;
+    a.n = n;
+    a.index_base = index_base;
+    a.words = words;
+    a.num_triangles = faces ? num_triangles : 0;
+    a.triangles = triangles;
+    a.cdf = cdf;
+    a.sigma = sigma;
+    a.samples_per_cell = samples_per_cell;
+    a.cell_level = cell_level;
+    a.corners = corners;
+    a.occupancy = occupancy_words;
+    a.occupancy_level = occupancy_level;
+    return 0;
+}
+
+int shacira_mesh_sample_count(int mode, int64_t n, int64_t index_base, uint64_t seed, uint32_t segment, const uint32_t *words,
+                              int64_t num_triangles, const float *triangles, const uint32_t *cdf, float sigma,
+                              int64_t num_cells, const int16_t *corners, int samples_per_cell, int cell_level,
+                              const uint32_t *occupancy_words, int occupancy_level, int32_t *block_counts, void *stream) {
+    MeshSampleArgs a;
+    const int rc = mesh_sample_args(mode, n, index_base, seed, segment, words, num_triangles, triangles, cdf, sigma, num_cells,
+                                    corners, samples_per_cell, cell_level, occupancy_words, occupancy_level, a);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!occupancy_words || !block_counts) return SHACIRA_EINVAL;
+    return (int)mesh_sample_count_dispatch(a, block_counts, (hipStream_t)stream);
+}
+
+int shacira_mesh_sample(int mode, int64_t n, int64_t index_base, uint64_t seed, uint32_t segment, const uint32_t *words,
+                        int64_t num_triangles, const float *triangles, const uint32_t *cdf, float sigma, int64_t num_cells,
+                        const int16_t *corners, int samples_per_cell, int cell_level, const uint32_t *occupancy_words,
+                        int occupancy_level, const int64_t *block_offsets, float *points, float *normals, int32_t *face_idx,
+                        int64_t *source_idx, void *stream) {
+    MeshSampleArgs a;
+    const int rc = mesh_sample_args(mode, n, index_base, seed, segment, words, num_triangles, triangles, cdf, sigma, num_cells,
+                                    corners, samples_per_cell, cell_level, occupancy_words, occupancy_level, a);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!points || (block_offsets == nullptr) != (occupancy_words == nullptr)) return SHACIRA_EINVAL;
+    return (int)mesh_sample_write_dispatch(a, block_offsets, points, normals, face_idx, source_idx, (hipStream_t)stream);
+}
+
 // ---- structural similarity -------------------------------------------------------------------------------------------------
 static bool ssim_args_ok(int64_t height, int64_t width, int pixel_stride, int channels) {
     if (height < SHACIRA_SSIM_WINDOW || width < SHACIRA_SSIM_WINDOW || channels < 1 || channels > pixel_stride) return false;

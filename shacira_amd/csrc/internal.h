@@ -153,6 +153,28 @@ size_t mesh_voxelize_workspace(int64_t t);
 hipError_t mesh_voxelize_dispatch(int64_t t, const float *tris, int level, float margin, uint32_t *words, uint8_t *grid,
                                   void *workspace, hipStream_t s);
 
+// mesh_sample.hip: n samples on, near or around a mesh, each a function of (seed, index), optionally only those inside the
+// occupied cells of one octree level (arguments checked by the entry points; by value in the kernel arguments)
+struct MeshSampleArgs {
+    int32_t mode;                 // SHACIRA_MESH_SAMPLE_*
+    uint32_t key0, key1;          // the seed's low and high word
+    uint32_t segment;
+    int64_t n, index_base;
+    const uint32_t *words;        // [n, 8] or NULL
+    int64_t num_triangles;
+    const float *triangles;       // [T, 3, 3]
+    const uint32_t *cdf;          // [T]
+    float sigma;
+    int32_t samples_per_cell, cell_level;
+    const int16_t *corners;       // [C, 3]
+    const uint32_t *occupancy;    // packed words of occupancy_level or NULL (no filter)
+    int32_t occupancy_level;
+};
+hipError_t mesh_sample_count_dispatch(const MeshSampleArgs &a, int32_t *block_counts, hipStream_t s);
+// block_offsets == NULL: sample i to row i; else the kept samples to block_offsets[i / 256] + rank within the block
+hipError_t mesh_sample_write_dispatch(const MeshSampleArgs &a, const int64_t *block_offsets, float *points, float *normals,
+                                      int32_t *face_idx, int64_t *source_idx, hipStream_t s);
+
 // ssim.hip: structural similarity of two [H, W, cin] fp32 images over their first C channels (arguments checked by the entry
 // points). Forward: value[0] fp64, map [H, W, C] or NULL; backward: grad_x [H, W, cin] for the device scalar grad[0]
 int64_t ssim_tiles(int64_t H, int64_t W);

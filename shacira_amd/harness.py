@@ -1060,3 +1060,79 @@ def fit_multiview(dataset, device, steps=300, rays=4096, num_steps=128, seed=0, 
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / max(1, steps) * 1e3
     return dict(nef=nef, tracer=tracer, losses=torch.stack(losses).cpu(), ms_per_step=ms, steps=steps, rays_per_step=rays)
+
+
+# =====================================================================================================================
+# Signed distance: NeuralSDF fitted to a mesh from the SDF datasets (the reference's SDFTrainer)
+# =====================================================================================================================
+def fit_sdf(dataset, device, steps=300, batch=4096, seed=0, num_lods=8, codebook_bitwidth=12, min_grid_res=4, max_grid_res=64,
+            hidden_dim=64, loss_lods=None, resample_every=0, lr=1e-3, grid_lr=1e-2):
+    """Fit a ``NeuralSDF`` on a ``HashGrid`` to the working set of ``dataset`` (``MeshSampledSDFDataset``,
+    ``OctreeSampledSDFDataset`` or anything with their ``data`` / ``resample``) with the fused Adam. The loss is that of the
+    reference's ``SDFTrainer.step``: the sum over ``loss_lods`` (default: the finest) of the squared error, divided by the
+    batch; three small torch ops on [B, 1]. Batches are seeded device ``randint`` rows of the working set;
+    ``resample_every`` > 0 calls ``dataset.resample()`` every that many steps. Returns dict(nef, losses [steps] on the host,
+    read back once after the loop, ms_per_step)."""
+    import time
+    from .optim import FusedAdam
+    from .wisp.models.grids import HashGrid
+    from .wisp.models.nefs.neural_sdf import NeuralSDF
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    grid = HashGrid.from_geometric(feature_dim=2, num_lods=num_lods, multiscale_type="cat", resolution_dim=3,
+                                   feature_std=0.01, codebook_bitwidth=codebook_bitwidth, min_grid_res=min_grid_res,
+                                   max_grid_res=max_grid_res, blas_level=3)
+    nef = NeuralSDF(grid, hidden_dim=hidden_dim, num_layers=1).to(device)
+    loss_lods = [num_lods - 1] if loss_lods is None else list(loss_lods)
+    groups = [g for g in param_groups(nef, lr=lr, grid_lr=grid_lr) if g["params"]]
+    opt = FusedAdam(groups, eps=1e-15) if device.type == "cuda" else torch.optim.Adam(groups, eps=1e-15)
+    gen = torch.Generator(device=device).manual_seed(seed + 1)
+    kept = []
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(steps):
+        if resample_every and it and it % resample_every == 0:
+            dataset.resample()
+        coords, sdf = dataset.data["coords"], dataset.data["sdf"]
+        rows = torch.randint(0, coords.shape[0], (batch,), device=device, generator=gen)
+        pts, gts = coords[rows], sdf[rows]
+        opt.zero_grad(set_to_none=True)
+        loss = 0
+        for lod_idx in loss_lods:
+            pred = nef(coords=pts, lod_idx=lod_idx, channels="sdf")
+            loss = loss + ((pred - gts) ** 2).sum()
+        loss = loss / batch
+        loss.backward()
+        opt.step()
+        kept.append(loss.detach())
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    return dict(nef=nef, losses=torch.stack(kept).cpu().tolist() if kept else [], steps=steps, loss_lods=loss_lods,
+                ms_per_step=elapsed / max(steps, 1) * 1e3)
+
+
+def validate_sdf(nef, dataset, loss_lods=None, chunk=1 << 18):
+    """The reference's ``SDFTrainer.validate``: the IoU of the field's inside set against the truth over the dataset's working
+    set (training and validation coincide: the field overfits one shape), averaged over ``loss_lods`` (default: the finest).
+    Returns {"volumetric_iou": ...} for a ``MeshSampledSDFDataset``, {"narrowband_iou": ...} for an
+    ``OctreeSampledSDFDataset`` and {"iou": ...} for any other holder of ``data``."""
+    from .wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
+    from .wisp.ops.sdf import compute_sdf_iou
+    name = ("volumetric_iou" if isinstance(dataset, MeshSampledSDFDataset) else
+            "narrowband_iou" if isinstance(dataset, OctreeSampledSDFDataset) else "iou")
+    coords, gts = dataset.data["coords"], dataset.data["sdf"]
+    loss_lods = [nef.grid.num_lods - 1] if loss_lods is None else list(loss_lods)
+    scores = []
+    was_training = nef.training
+    nef.eval()
+    try:
+        with torch.no_grad():
+            for lod_idx in loss_lods:
+                pred = torch.cat([nef(coords=coords[s:s + chunk], lod_idx=lod_idx, channels="sdf")
+                                  for s in range(0, coords.shape[0], chunk)]) if coords.shape[0] else gts
+                scores.append(compute_sdf_iou(pred, gts))
+    finally:
+        nef.train(was_training)
+    return {name: sum(scores) / len(scores)}

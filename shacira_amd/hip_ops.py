@@ -5,6 +5,7 @@ These functions have the signatures of the reference's pybind11 operators
 wisp/csrc/ops/hashgrid_interpolate.h:18-50) so ``wisp/ops/grid.py``-style callers read the same.
 Inputs must live on a HIP device; there is no CPU path (RuntimeError otherwise).
 """
+import collections
 import ctypes
 import functools
 import threading
@@ -1088,6 +1089,133 @@ def mesh_voxelize(triangles, level, margin=0.5, with_grid=True):
                                      _stream(triangles))
     _lib.check(rc, "mesh_voxelize")
     return words, (grid.view(torch.bool) if with_grid else None)
+
+
+# ---- mesh point sampling (include/shacira_hip.h, shacira_mesh_sample / shacira_mesh_sample_count) --------------------------------
+MESH_SAMPLE_MODES = {"surface": _lib.MESH_SAMPLE_SURFACE, "near": _lib.MESH_SAMPLE_NEAR, "cube": _lib.MESH_SAMPLE_CUBE,
+                     "cells": _lib.MESH_SAMPLE_CELLS}
+MeshSamples = collections.namedtuple("MeshSamples", ["points", "normals", "face_idx", "source_idx", "block_counts"])
+
+
+def mesh_face_cdf(triangles):
+    """The integer area CDF the sampler searches: an int32 tensor [T] holding uint32 bits, on the device of ``triangles``
+    [T, 3, 3]. cdf[t] = min(floor(sum[t] / sum[T - 1] * 2^32), 2^32 - 1), where sum is the running sum, in
+    index order and in fp64, of |cross(a - b, b - c)| (the operator order of ``per_face_normals``: the differences in fp32,
+    the cross product, its norm and the sum in fp64). Built once per mesh, on the host: the datasets cache it. A mesh without
+    area (or with a non-finite one) is refused with SHACIRA_EINVAL."""
+    if triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3):
+        raise RuntimeError(f"shacira_amd: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+    tri = triangles.detach().to(dtype=torch.float32).cpu().numpy()
+    x, y = (tri[:, 0] - tri[:, 1]).astype(np.float64), (tri[:, 1] - tri[:, 2]).astype(np.float64)
+    nx = x[:, 1] * y[:, 2] - x[:, 2] * y[:, 1]
+    ny = x[:, 2] * y[:, 0] - x[:, 0] * y[:, 2]
+    nz = x[:, 0] * y[:, 1] - x[:, 1] * y[:, 0]
+    run = np.cumsum(np.sqrt((nx * nx + ny * ny) + nz * nz))
+    if run.shape[0] == 0 or not (run[-1] > 0) or not np.isfinite(run[-1]):
+        _lib.check(_lib.EINVAL, "mesh_face_cdf (the mesh has no area)")
+    cdf = np.minimum(np.floor(run / run[-1] * 4294967296.0), 4294967295.0).astype(np.uint64).astype(np.uint32)
+    return torch.from_numpy(cdf.view(np.int32)).to(triangles.device)
+
+
+def _u32_operand(t, shape, dev, what):
+    """``t`` as contiguous 32-bit integer words of ``shape`` on ``dev`` (int32 and uint32 tensors carry the same bits)."""
+    if t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or t.device != dev or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"shacira_amd: mesh_sample expects {what} as int32 / uint32 {list(shape)} on {dev}, got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def mesh_sample(mode, n=None, seed=0, segment=0, index_base=0, triangles=None, cdf=None, sigma=0.0, corners=None,
+                samples_per_cell=None, cell_level=None, occupancy=None, occupancy_level=None, words=None, want_normals=False,
+                want_face=False, want_source=False, device=None):
+    """``MeshSamples`` of one sampling technique, every sample a pure function of (``seed``, ``index_base`` + i, ``segment``):
+
+    mode 'surface'  points uniform on ``triangles`` [T, 3, 3] (faces by area through ``cdf``, ``mesh_face_cdf(triangles)`` when
+                    None), their unnormalised face normals and face indices
+         'near'     surface points displaced by ``sigma`` times a standard normal per coordinate
+         'cube'     uniform in [-1, 1)^3
+         'cells'    ``samples_per_cell`` uniform points in every cell of ``corners`` (int16 [C, 3], cells of ``cell_level``);
+                    ``n`` is C * samples_per_cell
+
+    ``occupancy`` (the packed int32 words of ``occupancy_level``, ``OctreeAS.packed_occupancy``) keeps only the samples whose
+    cell is occupied -- ``OctreeAS.query(...).pidx > -1`` -- in index order: a counting launch, an exact int64 ``cumsum``, one
+    read-back of the total, a writing launch (not capturable into a graph; the unfiltered form is one launch and is).
+    ``block_counts`` is then the int32 count per 256 indices, else None. ``words`` (int32 / uint32 [n, 8]) replaces the random
+    words. ``normals`` / ``face_idx`` (int32) / ``source_idx`` (int64, the index i of every row) are None unless wanted. The
+    operands must be on the GPU; without tensor operands ('cube') ``device`` says where."""
+    if mode not in MESH_SAMPLE_MODES:
+        raise ValueError(f"mesh_sample: unknown mode {mode!r} (expected one of {sorted(MESH_SAMPLE_MODES)})")
+    code = MESH_SAMPLE_MODES[mode]
+    _need_gpu(triangles, cdf, corners, occupancy, words)
+    seed, segment, index_base = int(seed), int(segment), int(index_base)
+    if not 0 <= seed < 1 << 64 or not 0 <= segment < 1 << 32 or index_base < 0:
+        raise RuntimeError(f"shacira_amd: mesh_sample expects 0 <= seed < 2^64, 0 <= segment < 2^32 and index_base >= 0, got "
+                           f"{seed}, {segment}, {index_base}")
+    dev = next((t.device for t in (triangles, corners, occupancy, words) if t is not None), None)
+    if dev is None:
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            _need_gpu(torch.empty(0, device=dev))
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+    T = C = spc = level = 0
+    if code in (_lib.MESH_SAMPLE_SURFACE, _lib.MESH_SAMPLE_NEAR):
+        if triangles is None or triangles.dim() != 3 or tuple(triangles.shape[1:]) != (3, 3) or triangles.shape[0] < 1:
+            raise RuntimeError(f"shacira_amd: mesh_sample('{mode}') expects triangles [T >= 1, 3, 3], got "
+                               f"{None if triangles is None else tuple(triangles.shape)}")
+        triangles = triangles.detach().to(device=dev, dtype=torch.float32).contiguous()
+        T = triangles.shape[0]
+        cdf = mesh_face_cdf(triangles) if cdf is None else _u32_operand(cdf, (T,), dev, "cdf")
+    else:
+        triangles = cdf = None
+    if code == _lib.MESH_SAMPLE_CELLS:
+        if corners is None or corners.dim() != 2 or corners.shape[1] < 3 or samples_per_cell is None or cell_level is None:
+            raise RuntimeError("shacira_amd: mesh_sample('cells') expects corners [C, 3], samples_per_cell and cell_level")
+        corners = corners[:, :3].to(device=dev, dtype=torch.int16).contiguous()
+        C, spc, level = corners.shape[0], int(samples_per_cell), int(cell_level)
+        if spc < 1 or not 0 <= level <= _lib.OCTREE_MAX_LEVEL:
+            raise RuntimeError(f"shacira_amd: mesh_sample('cells') expects samples_per_cell >= 1 and cell_level in "
+                               f"0..{_lib.OCTREE_MAX_LEVEL}, got {spc}, {level}")
+        if n is None:
+            n = C * spc
+    else:
+        corners = None
+    if n is None or int(n) < 0:
+        raise RuntimeError(f"shacira_amd: mesh_sample expects n >= 0, got {n}")
+    n = int(n)
+    if words is not None:
+        words = _u32_operand(words, (n, 8), dev, "words")
+    olevel = 0
+    if occupancy is not None:
+        olevel = int(occupancy_level)
+        if not 0 <= olevel <= _lib.OCTREE_MAX_LEVEL:
+            raise RuntimeError(f"shacira_amd: occupancy_level must be in 0..{_lib.OCTREE_MAX_LEVEL}, got {olevel}")
+        occupancy = _u32_operand(occupancy, (((1 << (3 * olevel)) + 31) // 32,), dev, "occupancy")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("shacira_amd: the filtered mesh_sample reads the number of kept samples back between its two "
+                               "launches and cannot be captured into a graph")
+    L = _lib.lib()
+    head = (code, n, index_base, seed, segment, _ptr(words), T, _ptr(triangles), _ptr(cdf), float(sigma), C, _ptr(corners), spc,
+            level, _ptr(occupancy), olevel)
+    blocks = (n + _lib.MESH_SAMPLE_BLOCK - 1) // _lib.MESH_SAMPLE_BLOCK
+    counts = offsets = None
+    rows = n
+    with _on_device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if occupancy is not None:
+            counts = torch.empty((blocks,), dtype=torch.int32, device=dev)
+            _lib.check(L.shacira_mesh_sample_count(*head, _ptr(counts), stream), "mesh_sample_count")
+            ends = torch.cumsum(counts, dim=0, dtype=torch.int64)          # integers: exact
+            rows = int(ends[-1].item()) if blocks else 0
+            offsets = ends - counts
+        points = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((rows, 3), dtype=torch.float32, device=dev) if want_normals else None
+        face = torch.empty((rows,), dtype=torch.int32, device=dev) if want_face else None
+        source = torch.empty((rows,), dtype=torch.int64, device=dev) if want_source else None
+        if rows > 0:                                                       # nothing kept: the writer is not launched
+            _lib.check(L.shacira_mesh_sample(*head, _ptr(offsets), _ptr(points), _ptr(normals), _ptr(face), _ptr(source),
+                                             stream), "mesh_sample")
+    return MeshSamples(points, normals, face, source, counts)
 
 
 # ---- structural similarity (include/shacira_hip.h, shacira_ssim_forward / shacira_ssim_backward) -------------------------------

@@ -9,8 +9,8 @@ import importlib
 import sys
 
 _ALIASES = [
-    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.spc", "ops.geometric", "ops.differential", "ops.image", "ops.image.metrics", "ops.image.io", "ops.raygen", "ops.raygen.raygen", "core", "core.camera", "datasets",
-    "datasets.multiview_dataset", "datasets.image_dataset", "datasets.ray_sampler", "accelstructs", "accelstructs.aabb_as",
+    "ops", "ops.grid", "ops.triplane", "ops.octree", "ops.mesh", "ops.spc", "ops.geometric", "ops.differential", "ops.image", "ops.image.metrics", "ops.image.io", "ops.raygen", "ops.raygen.raygen", "ops.sdf", "ops.sdf.metrics", "core", "core.camera", "datasets",
+    "datasets.multiview_dataset", "datasets.image_dataset", "datasets.ray_sampler", "datasets.batch", "datasets.sdf_dataset", "accelstructs", "accelstructs.aabb_as",
     "models", "models.grids", "models.grids.blas_grid", "models.grids.hash_grid", "models.grids.latent_grid",
     "models.grids.triplanar_grid", "models.grids.octree_grid",
     "models.grids.codebook_grid", "models.latent_decoders",

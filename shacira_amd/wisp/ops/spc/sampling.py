@@ -3,9 +3,16 @@ run on any device)."""
 import torch
 
 
-def sample_spc(corners: torch.Tensor, level: int, num_samples: int) -> torch.Tensor:
+def sample_spc(corners: torch.Tensor, level: int, num_samples: int, seed=None, segment=0) -> torch.Tensor:
     """``num_samples`` uniform points inside every cell of ``corners`` [N, >= 3] (integer cells of ``level``), in [-1, 1]^3:
-    [N * num_samples, 3], the samples of one cell adjacent. A uniform point of cell c is (c + U[0, 1)^3) * 2 / G - 1."""
+    [N * num_samples, 3], the samples of one cell adjacent. A uniform point of cell c is (c + U[0, 1)^3) * 2 / G - 1. With
+    an int ``seed`` (``corners`` on the GPU) the fused kernel of mesh_sample.hip makes them, each a function of (seed, index,
+    ``segment``), in the same operator order."""
+    if seed is not None:
+        from .... import hip_ops
+        hip_ops._need_gpu(corners)
+        return hip_ops.mesh_sample("cells", seed=seed, segment=segment, corners=corners, samples_per_cell=num_samples,
+                                   cell_level=level).points
     cell_width = 2.0 / (1 << level)
     low = corners[:, :3].to(torch.float32) * cell_width - 1.0            # the cell's corner towards -1
     offsets = torch.rand((corners.shape[0], num_samples, 3), device=corners.device) * cell_width
