@@ -1325,6 +1325,105 @@ SHACIRA_API int shacira_sphere_trace_step(int64_t num_packs, int64_t num_nugs, i
                                           int32_t *count_out, int32_t *count_next, void *stream);
 
 /*
+ * View shading (ABI 11, additive): the per-pixel passes of the reference's OfflineRenderer over the buffers a tracer left on the
+ * device -- wisp/ops/geometric.py:130-155 (spherical_envmap), wisp/ops/shaders/matcap.py:20-72, wisp/offline_renderer.py:200-215
+ * (shading modes and segmentation) and :276-286 (the slice colours), wisp/ops/shaders/shadow_rays.py:31-67. The reference runs
+ * the matcap lookup, the shadow blur and the slice colours on the host (scipy, numpy) after a copy out. All operands are on the
+ * device unless named *_host; rows of three floats are dense ([n, 3], 4-byte aligned). fp32, one rounding per operator in the
+ * order written (correctly rounded / and sqrt, no fused multiply-add); a sum of three terms is (a + b) + c. One lane per pixel,
+ * no atomics, no allocation, no synchronisation: everything runs on `stream`, is capturable, and two calls return the same bits.
+ * Not differentiable. Common validation, before any HIP call: n < 0, an unknown mode or bad sizes return SHACIRA_EINVAL; then
+ * n == 0 returns 0 with nothing enqueued, whatever the pointers; then a NULL required operand returns SHACIRA_EINVAL.
+ *
+ * shacira_shade_view(n, mode, normal, dirs, hit, mm_host, tex, mh, mw, mc, rgb, uv_out, rgb8_out)
+ *   normal    fp32 [n, 3] in/out (read by NORMAL and MATCAP; written only where the segmentation applies)
+ *   dirs      fp32 [n, 3], the rays' directions (MATCAP only; may be NULL otherwise)
+ *   hit       uint8 [n] or NULL (no segmentation)
+ *   mm_host   9 floats ON THE HOST, row-major 3x3, read during the call, or NULL
+ *   tex       uint8 [mh, mw, mc], row-major as PIL gives it, mc 3 or 4, mh, mw in 2 .. 32768 (scipy's interpolator needs two grid
+ *             points per axis: 1 is refused). MATCAP with tex == NULL is the coordinates-only form: rgb, rgb8_out and hit must
+ *             be NULL and uv_out given, and the call is spherical_envmap for device tensors; mh, mw, mc are then ignored
+ *   rgb       fp32 [n, 3] in/out: read by RB, overwritten by the other modes
+ *   uv_out    fp32 [n, 2], 8-byte aligned, or NULL; MATCAP only
+ *   rgb8_out  uint8 [n, 3] or NULL: per channel v = rgb * 255, 0 for v <= 0 or NaN, 255 for v >= 255, else v truncated
+ *   SHACIRA_SHADE_MATCAP, with n the normal and d the direction:
+ *     v_i = (d_x mm[3i] + d_y mm[3i+1]) + d_z mm[3i+2]   (v = d without mm: the reference's dirs @ mm^T)
+ *     v_z = -v_z;  p = 2 ((n_x v_x + n_y v_y) + n_z v_z);  r = v - p n;  r_z = r_z - 1
+ *     m = 2 sqrt((r_x^2 + r_y^2) + r_z^2);  uv = 1 - (r_xy / m + 0.5);  uv = clamp to [0, 1] with NaN -> 0
+ *     (a zero normal against d = (0, 0, -1) gives m = 0, 0 / 0 and uv = (0, 0); a NaN normal gives uv = (0, 0))
+ *     x = u (mw - 1), x0 = min(floor x, mw - 2), fx = x - x0, the same in y with v and mh; with T the four texels as floats
+ *     c = (((1-fx)(1-fy) T[y0][x0] + fx (1-fy) T[y0][x0+1]) + (1-fx) fy T[y0+1][x0]) + fx fy T[y0+1][x0+1]) / 255
+ *     for the first three channels: scipy's RegularGridInterpolator over linspace(0, 1, mw) x linspace(0, 1, mh), which the
+ *     reference builds per call on the host
+ *   SHACIRA_SHADE_NORMAL: rgb = (normal + 1) / 2.      SHACIRA_SHADE_RB: rgb is kept.
+ *   Then, where hit is given and hit[i] == 0: normal[i] = (1, 1, 1) and rgb[i] = (1, 1, 1), whatever they held.
+ *   SHACIRA_EINVAL also for: mc outside {3, 4} or mh, mw out of range with tex; uv_out outside MATCAP; NULL normal (NORMAL,
+ *   MATCAP), dirs (MATCAP), rgb (every form but coordinates-only); a misaligned uv_out.
+ *
+ * shacira_shadow_rays(n, origins, dirs, light_host, min_y, seed, depth, xyz, normal, hit, so, sd, light_hit, plane_hit)
+ *   The ground plane y = min_y and one shadow ray per pixel towards the point light light_host[3] (on the host). origins, dirs
+ *   fp32 [n, 3]; depth fp32 [n], xyz and normal fp32 [n, 3], hit uint8 [n] are updated in place; so, sd fp32 [n, 3] and
+ *   light_hit, plane_hit uint8 [n] are overwritten. With o, d the ray:
+ *     rate = -d_y;  plane_t = (o_y - min_y) / rate
+ *     plane_hit = plane_t > 0 && plane_t < 500 && plane_t < depth      (NaN and the infinities of rate == 0 compare false;
+ *                                                                       the reference's |rate| < 1e-5 line changes nothing)
+ *     where plane_hit: hit = 0, depth = plane_t, xyz_k = o_k + d_k plane_t, normal = (0, 1, 0)
+ *     so_k = xyz_k + 0.01f normal_k
+ *     x_k = (light_k + 0.01f g_k) - so_k;  sd = x / max(sqrt((x_0^2 + x_1^2) + x_2^2), 1e-12f)
+ *     light_hit = ((sd_0 normal_0 + sd_1 normal_1) + sd_2 normal_2) > 0
+ *   g: three standard normals of ray i from Philox4x32-10 with counter (low word of i, high word of i, 0x53484457, 0) and the
+ *   key (low, high word of seed), by the Box-Muller step of shacira_mesh_sample: g_0 = r0 cos, g_1 = r0 sin, g_2 = r1 cos.
+ *   shacira_mesh_sample's counters hold 0 or 1 in the third word, so a shadow seed never replays a dataset's samples.
+ *
+ * shacira_shadow_apply(H, W, C, occluded, light_hit, shadow_out, rgb, workspace, workspace_bytes)
+ *   occluded, light_hit uint8 [H W]; shadow_out uint8 [H W], overwritten, must not overlap the two inputs (any shared byte
+ *   returns SHACIRA_EINVAL); rgb fp32 [H W, C] in place, C 3 or 4 (16-byte aligned for 4; the fourth channel keeps its bits);
+ *   1 <= H, W < 2^30 and H W < 2^31 (the reflect period 2 H or 2 W is an int), otherwise SHACIRA_EINVAL.
+ *     s = occluded && light_hit -> shadow_out;  map = clamp((1 - s) + 0.7, 0, 1)                       (1 or 0.7)
+ *     taps w[k] = exp(-k^2 / 8) / sum, k = -8 .. 8, normalised in fp64 and rounded to fp32: scipy.ndimage.gaussian_filter
+ *     (sigma = 2, truncate 4: radius SHACIRA_SHADOW_BLUR_RADIUS = 8)
+ *     one axis: out[i] = w[0] v[i], then for k = 1 .. 8 in turn out[i] = out[i] + w[k] (v[i - k] + v[i + k])
+ *     axis 0 (down the columns) into the workspace, then axis 1 on that; v[j] outside the image is read through scipy's
+ *     mode='reflect' (d c b a | a b c d | d c b a) continued periodically with period 2 n, so H or W below 9 work
+ *     rgb[., :3] = rgb[., :3] * blurred
+ *   workspace: shacira_shadow_apply_workspace_bytes(H, W) = 4 H W bytes (0 for invalid sizes), 4-byte aligned; a missing or
+ *   short one returns SHACIRA_EWORKSPACE. Two launches.
+ *
+ * shacira_sdf_slice_colors(n, d, vis): d fp32 [n] -> vis fp32 [n, 3], as numpy computes on a float32 array:
+ *     dd = clip((d + 1) / 2, 0, 1);  blue = clip((dd - 0.5) 2, 0, 1);  yellow = 1 - blue            (clip keeps a NaN)
+ *     vis = ((0 + yellow 0.4f) + 0.2f, (0 + yellow 0.3f) + 0.2f, (blue + yellow 0) + 0.2f)
+ *     dd - 0.5 < 0                                        -> vis = (1, 0.38f, 0)
+ *     |dd - (float)(0.02 i)| < (float)0.0015, any i in 0 .. 49  -> vis = 0.8f        (0.02 i formed in double, rounded once)
+ *     |dd - 0.5| < (float)0.004                           -> vis = 0
+ *   later rules overwrite earlier ones; a NaN d gives a NaN row. The reference accumulates vis in a float64 array: its colours
+ *   differ from these by the fp32 rounding of three operations.
+ *
+ * Where the reference is not followed (wisp/ops/shaders/shadow_rays.py, wisp/offline_renderer.py):
+ *   - it normalises the shadow directions over the RAY axis and keeps row [0] (F.normalize(dim=1)[0] of an [n, 3] tensor is
+ *     one ray's vector); here every ray's direction is normalised on its own;
+ *   - it blurs shadow_map[..., 0] of a flat [n] array (an index error); here the blur runs over the [H, W] view, so the
+ *     caller must hold n == H W;
+ *   - its jitter comes from the torch generator; here it is a function of (seed, ray index);
+ *   - its ambient-occlusion block reads an undefined name whenever shadows are on: ambient occlusion is not built.
+ */
+#define SHACIRA_SHADE_RB 0
+#define SHACIRA_SHADE_NORMAL 1
+#define SHACIRA_SHADE_MATCAP 2
+#define SHACIRA_SHADE_MAX_TEX 32768
+#define SHACIRA_SHADOW_BLUR_RADIUS 8
+SHACIRA_API int shacira_shade_view(int64_t n, int mode, float *normal, const float *dirs, const uint8_t *hit,
+                                   const float *mm_host, const uint8_t *tex, int mh, int mw, int mc, float *rgb, float *uv_out,
+                                   uint8_t *rgb8_out, void *stream);
+SHACIRA_API int shacira_shadow_rays(int64_t n, const float *origins, const float *dirs, const float *light_host, float min_y,
+                                    uint64_t seed, float *depth, float *xyz, float *normal, uint8_t *hit, float *so, float *sd,
+                                    uint8_t *light_hit, uint8_t *plane_hit, void *stream);
+SHACIRA_API size_t shacira_shadow_apply_workspace_bytes(int64_t height, int64_t width);
+SHACIRA_API int shacira_shadow_apply(int64_t height, int64_t width, int channels, const uint8_t *occluded,
+                                     const uint8_t *light_hit, uint8_t *shadow_out, float *rgb, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+SHACIRA_API int shacira_sdf_slice_colors(int64_t n, const float *d, float *vis, void *stream);
+
+/*
  * Diagnostics: one streaming pass over `bytes` (a multiple of 16; 16-byte aligned buffers) with the access shape of the
  * hash-grid kernels -- 16 bytes per lane, 8 in flight, non-temporal. kind 0 = read `src` (`dst` may be NULL or a 4-byte
  * scratch word), 1 = write `dst`, 2 = copy `src` -> `dst`. bench.py times it for `roofline.measured_stream_rates`.

@@ -27,6 +27,7 @@ RAYGEN_RECORD_FLOATS, RAYGEN_BG_WHITE, RAYGEN_BG_BLACK = 20, 0, 1       # SHACIR
 PIXEL_MAX_GRID, PIXEL_PARTIAL_BYTES = 2048, 24                          # SHACIRA_PIXEL_* of the header
 MESH_SAMPLE_SURFACE, MESH_SAMPLE_NEAR, MESH_SAMPLE_CUBE, MESH_SAMPLE_CELLS = 0, 1, 2, 3   # SHACIRA_MESH_SAMPLE_* of the header
 MESH_SAMPLE_BLOCK = 256
+SHADE_RB, SHADE_NORMAL, SHADE_MATCAP, SHADE_MAX_TEX, SHADOW_BLUR_RADIUS = 0, 1, 2, 32768, 8   # SHACIRA_SHADE_* / _SHADOW_*
 
 _lock = threading.Lock()
 _lib = None
@@ -90,6 +91,11 @@ SIGNATURES = {
     "shacira_find_depth_bound":(_i, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_sphere_trace_step": (_i, [_i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p]),
+    "shacira_shade_view": (_i, [_i64, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "shacira_shadow_rays": (_i, [_i64, _p, _p, _p, _f, ctypes.c_uint64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "shacira_shadow_apply_workspace_bytes": (_sz, [_i64, _i64]),
+    "shacira_shadow_apply": (_i, [_i64, _i64, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "shacira_sdf_slice_colors": (_i, [_i64, _p, _p, _p]),
     "shacira_latent_decode_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),
     "shacira_latent_decode_backward_workspace_bytes": (_sz, [_i64, _i, _i]),
     "shacira_latent_decode_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -858,6 +858,74 @@ static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_
                                            workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan);
 }
 
+// ---- view shading ---------------------------------------------------------------------------------------------------------------
+int shacira_shade_view(int64_t n, int mode, float *normal, const float *dirs, const uint8_t *hit, const float *mm_host,
+                       const uint8_t *tex, int mh, int mw, int mc, float *rgb, float *uv_out, uint8_t *rgb8_out, void *stream) {
+    if (n < 0) return SHACIRA_EINVAL;
+    if (mode != SHACIRA_SHADE_RB && mode != SHACIRA_SHADE_NORMAL && mode != SHACIRA_SHADE_MATCAP) return SHACIRA_EINVAL;
+    if (mode != SHACIRA_SHADE_MATCAP && uv_out) return SHACIRA_EINVAL;
+    if (mode == SHACIRA_SHADE_MATCAP && tex &&
+        ((mc != 3 && mc != 4) || mh < 2 || mw < 2 || mh > SHACIRA_SHADE_MAX_TEX || mw > SHACIRA_SHADE_MAX_TEX))
+        return SHACIRA_EINVAL;
+    if (n == 0) return 0;                       // an empty view may come with NULL operands
+    if (mode == SHACIRA_SHADE_MATCAP && !tex) {                 // the coordinates-only form
+        if (!uv_out || rgb || rgb8_out || hit) return SHACIRA_EINVAL;
+    } else if (!rgb) {
+        return SHACIRA_EINVAL;
+    }
+    if (mode != SHACIRA_SHADE_RB && !normal) return SHACIRA_EINVAL;
+    if (mode == SHACIRA_SHADE_MATCAP && !dirs) return SHACIRA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(uv_out) & 7u) != 0) return SHACIRA_EINVAL;
+    if (mode != SHACIRA_SHADE_MATCAP) tex = nullptr;
+    return (int)shade_view_dispatch(n, mode, normal, dirs, hit, mode == SHACIRA_SHADE_MATCAP ? mm_host : nullptr, tex, mh, mw, mc,
+                                    rgb, uv_out, rgb8_out, (hipStream_t)stream);
+}
+
+int shacira_shadow_rays(int64_t n, const float *origins, const float *dirs, const float *light_host, float min_y, uint64_t seed,
+                        float *depth, float *xyz, float *normal, uint8_t *hit, float *so, float *sd, uint8_t *light_hit,
+                        uint8_t *plane_hit, void *stream) {
+    if (n < 0) return SHACIRA_EINVAL;
+    if (n == 0) return 0;
+    if (!origins || !dirs || !light_host || !depth || !xyz || !normal || !hit || !so || !sd || !light_hit || !plane_hit)
+        return SHACIRA_EINVAL;
+    return (int)shadow_rays_dispatch(n, origins, dirs, light_host, min_y, seed, depth, xyz, normal, hit, so, sd, light_hit,
+                                     plane_hit, (hipStream_t)stream);
+}
+
+// each side below 2^30: the kernels' reflect period 2 n and the taps' y +- 8 stay inside an int
+static bool shadow_apply_sizes_ok(int64_t height, int64_t width) {
+    const int64_t side = (int64_t)1 << 30;
+    return height >= 1 && width >= 1 && height < side && width < side && height * width <= INT32_MAX;
+}
+
+static bool bytes_overlap(const void *a, const void *b, int64_t n) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb ? pb - pa < (uintptr_t)n : pa - pb < (uintptr_t)n;
+}
+
+size_t shacira_shadow_apply_workspace_bytes(int64_t height, int64_t width) {
+    return shadow_apply_sizes_ok(height, width) ? (size_t)(height * width) * sizeof(float) : 0;
+}
+
+int shacira_shadow_apply(int64_t height, int64_t width, int channels, const uint8_t *occluded, const uint8_t *light_hit,
+                         uint8_t *shadow_out, float *rgb, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!shadow_apply_sizes_ok(height, width) || (channels != 3 && channels != 4)) return SHACIRA_EINVAL;
+    if (!occluded || !light_hit || !shadow_out || !rgb) return SHACIRA_EINVAL;
+    if (bytes_overlap(shadow_out, occluded, height * width) || bytes_overlap(shadow_out, light_hit, height * width))
+        return SHACIRA_EINVAL;
+    if (channels == 4 && (reinterpret_cast<uintptr_t>(rgb) & 15u) != 0) return SHACIRA_EINVAL;
+    if (!workspace || workspace_bytes < shacira_shadow_apply_workspace_bytes(height, width)) return SHACIRA_EWORKSPACE;
+    return (int)shadow_apply_dispatch(height, width, channels, occluded, light_hit, shadow_out, rgb, workspace,
+                                      (hipStream_t)stream);
+}
+
+int shacira_sdf_slice_colors(int64_t n, const float *d, float *vis, void *stream) {
+    if (n < 0) return SHACIRA_EINVAL;
+    if (n == 0) return 0;
+    if (!d || !vis) return SHACIRA_EINVAL;
+    return (int)sdf_slice_colors_dispatch(n, d, vis, (hipStream_t)stream);
+}
+
 // ---- affine latent decoders: plain, SGA, SGA with the temperature on the device, per-level ---------------------------------
 static int levels_args_ok(int num_levels, const int64_t *row_offsets_host, int64_t num_rows, int latent_dim,
                           int feature_dim) {

@@ -202,6 +202,17 @@ hipError_t raygen_dispatch(const float *cams, int num_views, int width, int heig
                            const int32_t *pixel_idx, const float *jitter, int64_t n, const uint8_t *images, int channels,
                            bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s);
 
+// shade.hip: the offline renderer's per-pixel passes (arguments checked by the entry points; mm_host may be NULL, light_host not)
+hipError_t shade_view_dispatch(int64_t n, int mode, float *normal, const float *dirs, const uint8_t *hit, const float *mm_host,
+                               const uint8_t *tex, int mh, int mw, int mc, float *rgb, float *uv_out, uint8_t *rgb8_out,
+                               hipStream_t s);
+hipError_t shadow_rays_dispatch(int64_t n, const float *origins, const float *dirs, const float *light_host, float min_y,
+                                uint64_t seed, float *depth, float *xyz, float *normal, uint8_t *hit, float *so, float *sd,
+                                uint8_t *light_hit, uint8_t *plane_hit, hipStream_t s);
+hipError_t shadow_apply_dispatch(int64_t H, int64_t W, int C, const uint8_t *occluded, const uint8_t *light_hit,
+                                 uint8_t *shadow_out, float *rgb, void *workspace, hipStream_t s);
+hipError_t sdf_slice_colors_dispatch(int64_t n, const float *d, float *vis, hipStream_t s);
+
 // pixels.hip: coordinates and colours of pixels of one uint8 [H, W, 3] image, and the squared-error loss of predictions against
 // them (arguments checked by the entry points; pixel_idx == NULL is the range form, pixel i = start + i)
 size_t pixel_loss_workspace(int64_t n);

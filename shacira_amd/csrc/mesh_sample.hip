@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "internal.h"
+#include "philox.h"
 
 namespace shacira {
 
@@ -32,29 +33,6 @@ struct Sample {
     int32_t face;
     bool keep;
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-    constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
-        const uint32_t hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += kW0;
-        k1 += kW1;
-    }
-    out[0] = c0;
-    out[1] = c1;
-    out[2] = c2;
-    out[3] = c3;
-}
-
-__device__ __forceinline__ float unit_open_above(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }         // [0, 1)
-__device__ __forceinline__ float unit_open_below(uint32_t w) { return (float)((w >> 8) + 1u) * 0x1p-24f; }  // (0, 1]
 
 // the face of word w: the first t with cdf[t] > min(w, cdf[T - 1] - 1), never beyond T - 1. Integers only
 __device__ __forceinline__ int32_t face_of(const uint32_t *__restrict__ cdf, int32_t T, uint32_t w) {
@@ -116,16 +94,11 @@ __device__ __forceinline__ Sample make_sample(const MeshSampleArgs &a, int64_t i
             } else {
                 philox4x32_10((uint32_t)idx, (uint32_t)((uint64_t)idx >> 32), 1u, a.segment, a.key0, a.key1, g);
             }
-            // Box-Muller: two radii, two angles, three of the four normals
-            const float r0 = sqrtf(-2.0f * logf(unit_open_below(g[0])));
-            const float r1 = sqrtf(-2.0f * logf(unit_open_below(g[2])));
-            float s0, c0, s1, c1;
-            sincospif(2.0f * unit_open_above(g[1]), &s0, &c0);
-            sincospif(2.0f * unit_open_above(g[3]), &s1, &c1);
-            s.p[0] = s.p[0] + a.sigma * (r0 * c0);
-            s.p[1] = s.p[1] + a.sigma * (r0 * s0);
-            s.p[2] = s.p[2] + a.sigma * (r1 * c1);
-            (void)s1;
+            float z[3];
+            box_muller3(g, z);
+            s.p[0] = s.p[0] + a.sigma * z[0];
+            s.p[1] = s.p[1] + a.sigma * z[1];
+            s.p[2] = s.p[2] + a.sigma * z[2];
         }
     }
     s.keep = true;

@@ -1136,3 +1136,39 @@ def validate_sdf(nef, dataset, loss_lods=None, chunk=1 << 18):
     finally:
         nef.train(was_training)
     return {name: sum(scores) / len(scores)}
+
+
+RENDER_SDF_VIEWS = (dict(f=[2.2, 1.4, 2.2], t=[0, 0, 0]), dict(f=[-2.2, 1.4, 2.2], t=[0, 0, 0]), dict(f=[0.0, 2.8, 1.2], t=[0, 0, 0]))
+
+
+def render_sdf(nef, out_dir=None, res=(256, 256), views=RENDER_SDF_VIEWS, shading_mode="matcap", shadow=False, tracer=None):
+    """Look at a fitted signed distance field: sphere-trace ``nef`` (``PackedSDFTracer`` unless ``tracer`` is given) from each
+    of ``views`` (dicts of ``render_lookat`` keywords: ``f``, ``t``, optionally ``fov``, ``camera_proj``) with the
+    ``OfflineRenderer`` at ``res`` = (width, height), shaded by ``shading_mode`` ('matcap', 'normal' or 'rb'), optionally with
+    point-light shadows. Returns the [height, width, C] ``RenderBuffer`` s where the field lives. With ``out_dir`` every view
+    is also written as ``view{i}_rgb.png``, ``view{i}_normal.png`` and ``view{i}_depth.png``: the 8-bit form
+    ``rb.image().byte()``."""
+    import os
+    from .wisp.models.pipeline import Pipeline
+    from .wisp.offline_renderer import OfflineRenderer
+    from .wisp.ops.image.io import write_png
+    from .wisp.tracers import PackedSDFTracer
+    device = next(nef.parameters()).device if any(True for _ in nef.parameters()) else torch.device("cuda")
+    pipeline = Pipeline(nef, PackedSDFTracer() if tracer is None else tracer)
+    renderer = OfflineRenderer(render_res=list(res), shading_mode=shading_mode, shadow=shadow, device=device)
+    was_training = nef.training
+    nef.eval()
+    out = []
+    try:
+        for i, view in enumerate(views):
+            rb = renderer.render_lookat(pipeline, camera_clamp=[0, 10], **view)
+            out.append(rb)
+            if out_dir is not None:
+                os.makedirs(out_dir, exist_ok=True)
+                img = rb.image().byte().cpu()
+                for name in ("rgb", "normal", "depth"):
+                    if getattr(img, name, None) is not None:
+                        write_png(os.path.join(out_dir, f"view{i}_{name}.png"), getattr(img, name))
+    finally:
+        nef.train(was_training)
+    return out

@@ -1558,3 +1558,146 @@ def pixel_loss(pred, image, pixel_idx=None, start=0, out_image=None):
     if pixel_idx is not None:
         pixel_idx = pixel_idx.detach()
     return _PixelLoss.apply(pred, image, pixel_idx, int(start), out_image)
+
+
+# ---- view shading (include/shacira_hip.h, shacira_shade_view / shacira_shadow_* / shacira_sdf_slice_colors) ---------------------
+SHADE_MODES = {"rb": _lib.SHADE_RB, "normal": _lib.SHADE_NORMAL, "matcap": _lib.SHADE_MATCAP}
+
+
+def _rows(t, what, width=3, dtype=torch.float32, dev=None, n=None):
+    """A dense [n, width] (or [n] for width None) operand of the shading calls, checked: dtype, device, contiguity, shape."""
+    shape_ok = t.dim() == 1 if width is None else (t.dim() == 2 and t.shape[1] == width)
+    if t.dtype != dtype or not shape_ok or not t.is_contiguous() or (dev is not None and t.device != dev) or \
+            (n is not None and t.shape[0] != n):
+        want = f"[{'n' if n is None else n}{'' if width is None else ', ' + str(width)}]"
+        raise RuntimeError(f"shacira_amd: {what} must be a contiguous {dtype} {want} tensor"
+                           f"{'' if dev is None else ' on ' + str(dev)}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _flags(t, what, dev, n):
+    """A bool or uint8 [n] (or [n, 1]) flag array as the kernels read it: one byte per pixel, 0 or 1."""
+    if t.dtype not in (torch.bool, torch.uint8) or t.numel() != n or not t.is_contiguous() or t.device != dev:
+        raise RuntimeError(f"shacira_amd: {what} must be a contiguous bool or uint8 [{n}] tensor on {dev}, got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def shade_view(mode, normal=None, dirs=None, hit=None, rgb=None, matcap=None, mm=None, with_uv=False, with_rgb8=False):
+    """One pass over a traced view: shade by ``mode`` ('rb', 'normal', 'matcap'), then where ``hit`` is false set ``normal`` and
+    the colour to 1. ``normal`` fp32 [n, 3] is updated IN PLACE; ``rgb`` fp32 [n, 3] is updated in place when given ('rb' reads
+    it) and allocated otherwise. ``matcap``: uint8 [mh, mw, 3 or 4] texture on the device; ``mm``: 3x3 rotation of the view
+    (any device: nine floats are read on the host) or None. Returns (rgb, uv fp32 [n, 2] or None, rgb8 uint8 [n, 3] or None).
+    'matcap' with ``matcap=None`` and ``with_uv`` returns only the coordinates (rgb None): spherical_envmap. Not
+    differentiable."""
+    if mode not in SHADE_MODES:
+        raise RuntimeError(f"shacira_amd: shade_view mode must be one of {sorted(SHADE_MODES)}, got {mode!r}")
+    _need_gpu(normal, dirs, hit, rgb, matcap)
+    first = next((t for t in (normal, rgb, dirs) if t is not None), None)
+    if first is None:
+        raise RuntimeError("shacira_amd: shade_view needs normal or rgb")
+    dev, n = first.device, first.shape[0]
+    if mode != "rb" and normal is None:
+        raise RuntimeError(f"shacira_amd: shade_view mode {mode!r} needs normal")
+    if normal is not None:
+        _rows(normal, "shade_view normal", dev=dev, n=n)
+    if mode == "matcap":
+        if dirs is None:
+            raise RuntimeError("shacira_amd: shade_view mode 'matcap' needs dirs")
+        _rows(dirs, "shade_view dirs", dev=dev, n=n)
+    coords_only = mode == "matcap" and matcap is None
+    if coords_only and (not with_uv or with_rgb8 or hit is not None or rgb is not None):
+        raise RuntimeError("shacira_amd: shade_view without a matcap texture computes the coordinates only (with_uv=True)")
+    if with_uv and mode != "matcap":
+        raise RuntimeError("shacira_amd: shade_view with_uv needs mode 'matcap'")
+    mh = mw = mc = 0
+    if mode == "matcap" and matcap is not None:
+        if matcap.dtype != torch.uint8 or matcap.dim() != 3 or not matcap.is_contiguous() or matcap.device != dev:
+            raise RuntimeError(f"shacira_amd: shade_view matcap must be a contiguous uint8 [mh, mw, 3 or 4] tensor on {dev}, got "
+                               f"{matcap.dtype} {tuple(matcap.shape)} on {matcap.device}")
+        mh, mw, mc = matcap.shape
+    if hit is not None:
+        _flags(hit, "shade_view hit", dev, n)
+    if rgb is not None:
+        _rows(rgb, "shade_view rgb", dev=dev, n=n)
+    elif mode == "rb":
+        raise RuntimeError("shacira_amd: shade_view mode 'rb' needs rgb")
+    elif not coords_only:
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    mm_host = None
+    if mm is not None and mode == "matcap":
+        flat = [float(v) for v in mm.detach().to("cpu", torch.float32).reshape(-1)]
+        if len(flat) != 9:
+            raise RuntimeError(f"shacira_amd: shade_view mm must be 3 x 3, got {tuple(mm.shape)}")
+        mm_host = (ctypes.c_float * 9)(*flat)
+    uv = torch.empty((n, 2), dtype=torch.float32, device=dev) if with_uv else None
+    rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if with_rgb8 else None
+    with _on_device(dev):
+        rc = _lib.lib().shacira_shade_view(n, SHADE_MODES[mode], _ptr(normal), _ptr(dirs) if mode == "matcap" else None, _ptr(hit),
+                                           mm_host, _ptr(matcap) if mode == "matcap" else None, mh, mw, mc, _ptr(rgb), _ptr(uv),
+                                           _ptr(rgb8), _stream(first))
+    _lib.check(rc, "shade_view")
+    return rgb, uv, rgb8
+
+
+def shadow_rays(origins, dirs, depth, xyz, normal, hit, point_light=(1.5, 4.5, 1.5), min_y=-2.0, seed=0):
+    """The ground plane y = ``min_y`` and one shadow ray per pixel towards the jittered point light. ``depth`` fp32 [n] or
+    [n, 1], ``xyz`` / ``normal`` fp32 [n, 3] and ``hit`` bool [n] are updated IN PLACE where the plane is in front. Returns
+    (shadow origins fp32 [n, 3], shadow dirs fp32 [n, 3], light_hit bool [n], plane_hit bool [n]). The jitter is a function of
+    (seed, ray index). Not differentiable."""
+    _need_gpu(origins, dirs, depth, xyz, normal, hit)
+    dev, n = origins.device, origins.shape[0]
+    for name, t in (("origins", origins), ("dirs", dirs), ("xyz", xyz), ("normal", normal)):
+        _rows(t, f"shadow_rays {name}", dev=dev, n=n)
+    if depth.dtype != torch.float32 or depth.numel() != n or not depth.is_contiguous() or depth.device != dev:
+        raise RuntimeError(f"shacira_amd: shadow_rays depth must be a contiguous fp32 [{n}] tensor on {dev}, got {depth.dtype} "
+                           f"{tuple(depth.shape)} on {depth.device}")
+    _flags(hit, "shadow_rays hit", dev, n)
+    light = (ctypes.c_float * 3)(*[float(v) for v in point_light])
+    so = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    sd = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    light_hit = torch.empty((n,), dtype=torch.bool, device=dev)
+    plane_hit = torch.empty((n,), dtype=torch.bool, device=dev)
+    with _on_device(dev):
+        rc = _lib.lib().shacira_shadow_rays(n, _ptr(origins), _ptr(dirs), light, float(min_y), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                            _ptr(depth), _ptr(xyz), _ptr(normal), _ptr(hit), _ptr(so), _ptr(sd), _ptr(light_hit),
+                                            _ptr(plane_hit), _stream(origins))
+    _lib.check(rc, "shadow_rays")
+    return so, sd, light_hit, plane_hit
+
+
+def shadow_apply(height, width, occluded, light_hit, rgb):
+    """shadow = occluded & light_hit; the map 1 / 0.7 blurred over the [height, width] view as
+    scipy.ndimage.gaussian_filter(sigma=2) does; ``rgb`` fp32 [height * width, 3 or 4] is multiplied IN PLACE (first three
+    channels). Returns shadow bool [height * width]. Not differentiable."""
+    _need_gpu(occluded, light_hit, rgb)
+    H, W = int(height), int(width)
+    dev, n = rgb.device, H * W
+    if H < 1 or W < 1:
+        raise RuntimeError(f"shacira_amd: shadow_apply needs a view of at least 1 x 1, got {H} x {W}")
+    if rgb.dtype != torch.float32 or rgb.dim() != 2 or rgb.shape[0] != n or rgb.shape[1] not in (3, 4) or not rgb.is_contiguous():
+        raise RuntimeError(f"shacira_amd: shadow_apply rgb must be a contiguous fp32 [{n}, 3 or 4] tensor (the shadows are blurred "
+                           f"over the {H} x {W} view), got {rgb.dtype} {tuple(rgb.shape)}")
+    _flags(occluded, "shadow_apply occluded", dev, n)
+    _flags(light_hit, "shadow_apply light_hit", dev, n)
+    shadow = torch.empty((n,), dtype=torch.bool, device=dev)
+    nbytes = int(_lib.lib().shacira_shadow_apply_workspace_bytes(H, W))
+    ws = _workspace(dev, nbytes)
+    with _on_device(dev):
+        rc = _lib.lib().shacira_shadow_apply(H, W, rgb.shape[1], _ptr(occluded), _ptr(light_hit), _ptr(shadow), _ptr(rgb),
+                                             _ptr(ws), nbytes, _stream(rgb))
+    _lib.check(rc, "shadow_apply")
+    return shadow
+
+
+def sdf_slice_colors(d):
+    """The colour map of an SDF slice: fp32 distances of any shape -> fp32 [*shape, 3] (orange inside, blue to yellow outside,
+    grey isolines every 0.04, black at the surface). Not differentiable."""
+    _need_gpu(d)
+    if d.dtype != torch.float32 or not d.is_contiguous():
+        raise RuntimeError(f"shacira_amd: sdf_slice_colors expects a contiguous fp32 tensor, got {d.dtype} {tuple(d.shape)}")
+    vis = torch.empty((*d.shape, 3), dtype=torch.float32, device=d.device)
+    with _on_device(d.device):
+        rc = _lib.lib().shacira_sdf_slice_colors(d.numel(), _ptr(d), _ptr(vis), _stream(d))
+    _lib.check(rc, "sdf_slice_colors")
+    return vis

@@ -20,6 +20,7 @@ _ALIASES = [
     "models.embedders", "models.activations", "models.nefs", "models.nefs.image", "models.nefs.nerf", "models.nefs.neural_sdf",
     "tracers", "tracers.packed_rf_tracer",
     "tracers.packed_sdf_tracer", "utils", "utils.schedulers",
+    "ops.image.processing", "ops.shaders", "ops.shaders.matcap", "ops.shaders.shadow_rays", "models.pipeline", "offline_renderer",
 ]
 
 
