@@ -968,6 +968,40 @@ SHACIRA_API int shacira_adam_step_multi(int num_tensors, const int64_t *numel_ho
                             const int32_t *step_dev, int zero_grad, void *stream);
 
 /*
+ * Loss-scaled steps for mixed-precision training (the reference trains under autocast + torch.cuda.amp.GradScaler,
+ * wisp/trainers/base_trainer.py:167-168) with no host round trip. Two more DEVICE pointers, either may be NULL:
+ *   found_inf_dev   one float. Every workgroup reads it first; non-zero SKIPS the step: param and all state stay bit
+ *                   for bit as they were, and so does grad unless zero_grad != 0, which still clears it (a persistent
+ *                   gradient buffer must not carry an inf into the next accumulation). NULL: never skip.
+ *   grad_scale_dev  one float, the loss scale. The gradient is unscaled first, gu = grad / *grad_scale_dev, rounded to
+ *                   fp32 on its own (never fused into the weight-decay product: a power-of-two scale changes no bit of
+ *                   the step). With zero_grad == 0, gu is written back to grad (as torch's fused optimizers do);
+ *                   otherwise grad is cleared. NULL: the gradients are already unscaled, grad is not rewritten.
+ *                   With a scale that is no power of two the division's remainder (grad - gu*scale, exact) is carried
+ *                   into the state beside gu, so the moments follow grad / scale more closely than fp32 gu alone would.
+ * A skipped step must not advance a device-resident step count: the caller adds (found_inf == 0) to it on the stream.
+ * With both pointers NULL shacira_adam_step_multi_scaled IS shacira_adam_step_multi.
+ */
+SHACIRA_API int shacira_adam_step_multi_scaled(int num_tensors, const int64_t *numel_host, float *const *param,
+                            float *const *grad, float *const *exp_avg, float *const *exp_avg_sq, const float *lr_host,
+                            const float *weight_decay_host, float beta1, float beta2, float eps, int step,
+                            const int32_t *step_dev, int zero_grad, const float *grad_scale_dev,
+                            const float *found_inf_dev, void *stream);
+
+/*
+ * Multi-tensor RMSprop (nerf_base.yaml's optimizer_type 'rmsprop'): torch.optim.RMSprop with centered=False,
+ * maximize=False, up to 32 parameters in one launch, table layout as shacira_adam_step_multi:
+ *     g' = grad + weight_decay*param ; sq = alpha*sq + (1-alpha)*g'^2 ; avg = sqrt(sq) + eps
+ *     momentum == 0: param -= lr * g'/avg          otherwise: buf = momentum*buf + g'/avg ; param -= lr*buf
+ *   momentum_buf may be NULL when momentum == 0 (it is not read). grad_scale_dev / found_inf_dev / zero_grad as above.
+ */
+SHACIRA_API int shacira_rmsprop_step_multi(int num_tensors, const int64_t *numel_host, float *const *param,
+                            float *const *grad, float *const *square_avg, float *const *momentum_buf,
+                            const float *lr_host, const float *weight_decay_host, float alpha, float eps,
+                            float momentum, const float *grad_scale_dev, const float *found_inf_dev, int zero_grad,
+                            void *stream);
+
+/*
  * Latent decode with stochastic Gumbel annealing (SGA) instead of rounding -- the `use_sga` branch of
  * LatentDecoder.forward (wisp/models/latent_decoders/basic_latent_decoder.py:183-191), the training mode of the
  * reference's shipped configs (kodak.yaml / nerf_lego.yaml: use_sga, diff_sampling) until `decay_period`:

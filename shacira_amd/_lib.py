@@ -146,6 +146,8 @@ SIGNATURES = {
     "shacira_adam_step": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _f, _f, _i, _i, _p]),
     "shacira_adam_step_multi": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _i, _p, _i, _p]),
     "shacira_adam_step_capturable": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _f, _f, _p, _i, _p]),
+    "shacira_adam_step_multi_scaled": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p]),
+    "shacira_rmsprop_step_multi": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _i, _p]),
 }
 
 

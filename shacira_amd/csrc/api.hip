@@ -1396,10 +1396,11 @@ int shacira_adam_step_capturable(int64_t numel, float *param, float *grad, float
                                  step_dev, zero_grad, (hipStream_t)stream);
 }
 
-int shacira_adam_step_multi(int num_tensors, const int64_t *numel_host, float *const *param, float *const *grad,
-                            float *const *exp_avg, float *const *exp_avg_sq, const float *lr_host,
-                            const float *weight_decay_host, float beta1, float beta2, float eps, int step,
-                            const int32_t *step_dev, int zero_grad, void *stream) {
+int shacira_adam_step_multi_scaled(int num_tensors, const int64_t *numel_host, float *const *param, float *const *grad,
+                                   float *const *exp_avg, float *const *exp_avg_sq, const float *lr_host,
+                                   const float *weight_decay_host, float beta1, float beta2, float eps, int step,
+                                   const int32_t *step_dev, int zero_grad, const float *grad_scale_dev,
+                                   const float *found_inf_dev, void *stream) {
     if (num_tensors < 0 || num_tensors > 32) return SHACIRA_EINVAL;
     if (num_tensors == 0) return 0;
     if (!numel_host || !param || !grad || !exp_avg || !exp_avg_sq || !lr_host || !weight_decay_host)
@@ -1410,8 +1411,35 @@ int shacira_adam_step_multi(int num_tensors, const int64_t *numel_host, float *c
         if (numel_host[t] < 0 || (numel_host[t] > 0 && (!param[t] || !grad[t] || !exp_avg[t] || !exp_avg_sq[t])))
             return SHACIRA_EINVAL;
     return (int)adam_multi_launch(num_tensors, param, grad, exp_avg, exp_avg_sq, numel_host, lr_host,
-                                  weight_decay_host, beta1, beta2, eps, step, step_dev, zero_grad,
-                                  (hipStream_t)stream);
+                                  weight_decay_host, beta1, beta2, eps, step, step_dev, grad_scale_dev, found_inf_dev,
+                                  zero_grad, (hipStream_t)stream);
+}
+
+int shacira_adam_step_multi(int num_tensors, const int64_t *numel_host, float *const *param, float *const *grad,
+                            float *const *exp_avg, float *const *exp_avg_sq, const float *lr_host,
+                            const float *weight_decay_host, float beta1, float beta2, float eps, int step,
+                            const int32_t *step_dev, int zero_grad, void *stream) {
+    return shacira_adam_step_multi_scaled(num_tensors, numel_host, param, grad, exp_avg, exp_avg_sq, lr_host,
+                                          weight_decay_host, beta1, beta2, eps, step, step_dev, zero_grad, nullptr,
+                                          nullptr, stream);
+}
+
+int shacira_rmsprop_step_multi(int num_tensors, const int64_t *numel_host, float *const *param, float *const *grad,
+                               float *const *square_avg, float *const *momentum_buf, const float *lr_host,
+                               const float *weight_decay_host, float alpha, float eps, float momentum,
+                               const float *grad_scale_dev, const float *found_inf_dev, int zero_grad, void *stream) {
+    if (num_tensors < 0 || num_tensors > 32) return SHACIRA_EINVAL;
+    if (num_tensors == 0) return 0;
+    if (!numel_host || !param || !grad || !square_avg || !lr_host || !weight_decay_host) return SHACIRA_EINVAL;
+    if (!(alpha >= 0.0f) || !(eps >= 0.0f) || !(momentum >= 0.0f)) return SHACIRA_EINVAL;
+    if (momentum != 0.0f && !momentum_buf) return SHACIRA_EINVAL;
+    for (int t = 0; t < num_tensors; ++t)
+        if (numel_host[t] < 0 || (numel_host[t] > 0 && (!param[t] || !grad[t] || !square_avg[t] ||
+                                                        (momentum != 0.0f && !momentum_buf[t]))))
+            return SHACIRA_EINVAL;
+    return (int)rmsprop_multi_launch(num_tensors, param, grad, square_avg, momentum_buf, numel_host, lr_host,
+                                     weight_decay_host, alpha, eps, momentum, grad_scale_dev, found_inf_dev, zero_grad,
+                                     (hipStream_t)stream);
 }
 
 int shacira_stream_probe(int kind, const void *src, void *dst, size_t bytes, void *stream) {

@@ -343,7 +343,13 @@ hipError_t adam_step_launch(float *p, float *g, float *m, float *v, int64_t n, f
 
 hipError_t adam_multi_launch(int count, float *const *p, float *const *g, float *const *m, float *const *v,
                              const int64_t *n, const float *lr, const float *wd, float b1, float b2, float eps,
-                             int step, const int32_t *step_dev, int zero_grad, hipStream_t s);
+                             int step, const int32_t *step_dev, const float *grad_scale, const float *found_inf,
+                             int zero_grad, hipStream_t s);
+
+hipError_t rmsprop_multi_launch(int count, float *const *p, float *const *g, float *const *sq, float *const *buf,
+                                const int64_t *n, const float *lr, const float *wd, float alpha, float eps,
+                                float momentum, const float *grad_scale, const float *found_inf, int zero_grad,
+                                hipStream_t s);
 
 // mlp.hip / mlp_mfma.hip
 constexpr int kMlpMaxBlocks = 512;        // backward grid (= rows of the fp64 partial-gradient workspace), VALU and wide MFMA

@@ -553,21 +553,43 @@ class NeuralField3D(nn.Module):
 
 
 def fit_field_3d(device, steps=500, rays=4096, samples_per_ray=16, seed=0, codebook_bitwidth=19, max_grid_res=2048,
-                 num_lods=16, rank=0, world=1, val_points=65536):
+                 num_lods=16, rank=0, world=1, val_points=65536, amp=False, optimizer="adam"):
     """Config D/E: every step draws `rays` x `samples_per_ray` fresh ray points (global batch, sharded over ranks),
-    L1 loss to the analytic field, Adam; returns dict(psnr on a fixed validation set, ms_per_step)."""
+    L1 loss to the analytic field, Adam or (`optimizer="rmsprop"`, nerf_base.yaml's optimizer_type) RMSprop; returns
+    dict(psnr on a fixed validation set, ms_per_step).
+
+    `amp=True` (CUDA, one rank) trains as the reference's trainers do by default (base_trainer.py:167-168,
+    multiview_trainer.py:141-156): forward and loss under fp16 autocast, the step through torch.amp.GradScaler -- which
+    hands its scale and inf flag to the fused optimizer on the device, so no step reads anything back. The dict then also
+    holds `skipped_steps` (steps minus the device step count), `final_scale` and the last step's `loss`, all read once after
+    the loop."""
     import time
     from .dist import FlatGradients, shard_batch
-    from .optim import FusedAdam
+    from .optim import FusedAdam, FusedRMSprop
     from .wisp.models.grids import HashGrid
     from .wisp.ops.image.metrics import psnr as psnr_fn
+    if optimizer not in ("adam", "rmsprop"):
+        raise ValueError(f"fit_field_3d: optimizer must be 'adam' or 'rmsprop', got {optimizer!r}")
+    if amp and device.type != "cuda":
+        raise ValueError("fit_field_3d: amp=True needs a CUDA device")
+    if amp and world > 1:
+        raise NotImplementedError("fit_field_3d: amp=True with world > 1 has never been run on a multi-GPU node")
     torch.manual_seed(seed)
     grid = HashGrid.from_geometric(feature_dim=2, num_lods=num_lods, multiscale_type="cat", resolution_dim=3,
                                    feature_std=0.01, codebook_bitwidth=codebook_bitwidth, min_grid_res=16,
                                    max_grid_res=max_grid_res, blas_level=3)
     nef = NeuralField3D(grid).to(device)
     groups = [g for g in param_groups(nef, lr=1e-3, grid_lr=1e-2) if g["params"]]
-    opt = FusedAdam(groups, eps=1e-15) if device.type == "cuda" else torch.optim.Adam(groups, eps=1e-15)
+    if optimizer == "adam":
+        if amp:
+            opt = FusedAdam(groups, eps=1e-15, capturable=True)
+        else:
+            opt = FusedAdam(groups, eps=1e-15) if device.type == "cuda" else torch.optim.Adam(groups, eps=1e-15)
+    elif device.type == "cuda":
+        opt = FusedRMSprop(groups, capturable=amp)
+    else:
+        opt = torch.optim.RMSprop(groups)
+    scaler = torch.amp.GradScaler("cuda") if amp else None
     bucket = FlatGradients([p for g in groups for p in g["params"]]) if world > 1 else None
     gen = torch.Generator().manual_seed(seed + 1)                     # the SAME sample stream on every rank
     n_global = rays * samples_per_ray
@@ -582,6 +604,13 @@ def fit_field_3d(device, steps=500, rays=4096, samples_per_ray=16, seed=0, codeb
             bucket.zero_()
         else:
             opt.zero_grad(set_to_none=True)
+        if amp:
+            with torch.autocast("cuda", dtype=torch.float16):
+                loss = (nef.rgb(local) - target).abs().sum() / (n_global * 3)
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+            continue
         loss = (nef.rgb(local) - target).abs().sum() / (n_global * 3)     # global-mean L1 (multiview_trainer.py:105-108)
         loss.backward()
         hidden = []
@@ -593,12 +622,17 @@ def fit_field_3d(device, steps=500, rays=4096, samples_per_ray=16, seed=0, codeb
             bucket.restore(hidden)
     if device.type == "cuda":
         torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    ms = (time.perf_counter() - t0) / max(steps, 1) * 1e3
     with torch.no_grad():
         vp = (torch.rand(val_points, 3, generator=torch.Generator().manual_seed(99)) * 2 - 1).to(device)
         pred = nef.rgb(vp)
         val = psnr_fn(pred.clamp(0, 1), analytic_field(vp))
-    return dict(psnr=val, ms_per_step=ms, steps=steps, samples_per_step=n_global)
+    out = dict(psnr=val, ms_per_step=ms, steps=steps, samples_per_step=n_global)
+    if amp:
+        counts = {int(st["step"].item()) for st in opt.state.values() if "step" in st}
+        out.update(skipped_steps=steps - (max(counts) if counts else 0), final_scale=float(scaler.get_scale()),
+                   loss=float(loss.detach()) if steps else float("nan"))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ NeRF render-and-fit
