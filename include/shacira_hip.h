@@ -810,6 +810,39 @@ SHACIRA_API int shacira_raygen(const float *cams, int num_views, int width, int 
                                int bg_mode, float *origins, float *dirs, float *rgb, uint8_t *mask, void *stream);
 
 /*
+ * Mip levels of the training images: a power-of-two area resize (OpenCV's INTER_AREA by 2^-mip, what
+ * wisp/datasets/formats/nerf_standard_dataset.py:221 asks of cv2) is the mean of a 2^mip x 2^mip block of pixels. Its numerator
+ * is an integer that fits 16 bits for mip <= SHACIRA_IMAGE_MIP_MAX (255 * 4^4 = 65280), so a level is kept EXACTLY, as one uint16
+ * sum per channel -- 8 bytes per RGBA pixel of the level -- and divided once, where a colour is needed.
+ * shacira_image_mip:
+ *   images         uint8 [num_views, height, width, channels] on the device, channels 1 .. 4
+ *   mip            1 .. SHACIRA_IMAGE_MIP_MAX; height and width are multiples of 2^mip
+ *   sums           uint16 [num_views, height >> mip, width >> mip, channels], overwritten:
+ *                     sums[v, y, x, c] = sum over dy, dx < 2^mip of images[v, (y << mip) + dy, (x << mip) + dx, c]
+ * Every byte offset is 64-bit: num_views * height * width * channels may pass 2^31. One pass over the source bytes, lanes along
+ * x; four channels on a 4-byte aligned `images` and 8-byte aligned `sums` read dwords (16 bytes per lane when `images` is 16-byte
+ * aligned) and store a pixel's four sums at once, anything else reads bytes -- the result is the same. No workspace, no
+ * allocation, no synchronisation, no atomics, no LDS: capturable, two calls return the same bits. Validation precedes any HIP
+ * call: SHACIRA_EINVAL for mip outside 1 .. 4, channels outside 1 .. 4, num_views, height or width <= 0, height or width not a
+ * multiple of 2^mip, (height >> mip) * (width >> mip) >= 2^31, a byte count beyond 2^60, a NULL pointer or an odd `sums`.
+ * shacira_raygen_sums: shacira_raygen with the colours of a mip level. Every argument and every rule above (shacira_raygen) holds
+ * with `sums` uint16 [num_views, H, W, channels] (2-byte aligned; W, H are the LEVEL's size) in the place of `images`, and
+ *     c = float(S) / float(255 << (2 mip)),  a likewise
+ * -- two exactly representable numbers and one correctly rounded division, so c is the correctly rounded block mean -- in the
+ * place of float(byte) / 255; the composite, the clamp, the NaN rows and the whole-view form are the same code. mask = a > 0.5
+ * is the integer test 2 S_a > 255 * 4^mip: at equality a is exactly 0.5, and one unit of S_a above it a exceeds 0.5 by 1 / (255 *
+ * 4^mip) >= 2^-16, far above fp32's spacing there. Four channels on an 8-byte aligned base take one 8-byte load per ray.
+ * SHACIRA_EINVAL additionally for mip outside 1 .. SHACIRA_IMAGE_MIP_MAX.
+ */
+#define SHACIRA_IMAGE_MIP_MAX 4
+SHACIRA_API int shacira_image_mip(const uint8_t *images, int64_t num_views, int64_t height, int64_t width, int channels,
+                                  int mip, uint16_t *sums, void *stream);
+SHACIRA_API int shacira_raygen_sums(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                                    const int32_t *pixel_idx, const float *jitter, int64_t n, const uint16_t *sums,
+                                    int channels, int mip, int bg_mode, float *origins, float *dirs, float *rgb,
+                                    uint8_t *mask, void *stream);
+
+/*
  * Pixel batches and the pixel loss: an image fit's coordinates, target colours, squared error and "clamped PSNR" statistics made
  * from pixel indices and ONE uint8 image that stays on the device -- what wisp/datasets/formats/multi_image_dataset.py:140-161
  * stores per pixel (40 bytes on the host) and :190-242 gathers per batch, and what wisp/ops/image/metrics.py:39-58 computes from a

@@ -24,6 +24,7 @@ OCTREE_MAX_LEVEL = 10                                         # SHACIRA_OCTREE_M
 SSIM_WINDOW, SSIM_TILE_H, SSIM_TILE_W = 11, 16, 64            # SHACIRA_SSIM_* of the header
 POSENC_MAX_DIM, POSENC_MAX_BANDS, POSENC_MAX_PREFIX = 4, 64, 1 << 30   # SHACIRA_POSENC_* of the header
 RAYGEN_RECORD_FLOATS, RAYGEN_BG_WHITE, RAYGEN_BG_BLACK = 20, 0, 1       # SHACIRA_RAYGEN_* of the header
+IMAGE_MIP_MAX = 4                                                       # SHACIRA_IMAGE_MIP_MAX of the header
 PIXEL_MAX_GRID, PIXEL_PARTIAL_BYTES = 2048, 24                          # SHACIRA_PIXEL_* of the header
 MESH_SAMPLE_SURFACE, MESH_SAMPLE_NEAR, MESH_SAMPLE_CUBE, MESH_SAMPLE_CELLS = 0, 1, 2, 3   # SHACIRA_MESH_SAMPLE_* of the header
 MESH_SAMPLE_BLOCK = 256
@@ -84,6 +85,8 @@ SIGNATURES = {
     "shacira_posenc_backward2": (_i, [_i64, _i, _i, _i, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "shacira_raygen_record_floats": (_i, []),
     "shacira_raygen": (_i, [_p, _i, _i, _i, _p, _p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "shacira_image_mip": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _p]),
+    "shacira_raygen_sums": (_i, [_p, _i, _i, _i, _p, _p, _p, _i64, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "shacira_pixel_batch": (_i, [_p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p]),
     "shacira_pixel_loss_workspace_bytes": (_sz, [_i64]),
     "shacira_pixel_loss_forward": (_i, [_p, _i64, _p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p, _sz, _p]),

@@ -682,6 +682,39 @@ int shacira_raygen(const float *cams, int num_views, int width, int height, cons
                                 bg_mode == SHACIRA_RAYGEN_BG_BLACK, origins, dirs, rgb, mask, (hipStream_t)stream);
 }
 
+int shacira_raygen_sums(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                        const int32_t *pixel_idx, const float *jitter, int64_t n, const uint16_t *sums, int channels, int mip,
+                        int bg_mode, float *origins, float *dirs, float *rgb, uint8_t *mask, void *stream) {
+    if (num_views <= 0 || width <= 0 || height <= 0 || n < 0) return SHACIRA_EINVAL;
+    if ((int64_t)width * height > INT32_MAX) return SHACIRA_EINVAL;          // pixel indices are int32
+    if (mip < 1 || mip > SHACIRA_IMAGE_MIP_MAX) return SHACIRA_EINVAL;
+    if (sums && channels != 3 && channels != 4) return SHACIRA_EINVAL;
+    if (bg_mode != SHACIRA_RAYGEN_BG_WHITE && bg_mode != SHACIRA_RAYGEN_BG_BLACK) return SHACIRA_EINVAL;
+    if ((view_idx == nullptr) != (pixel_idx == nullptr)) return SHACIRA_EINVAL;
+    if (!view_idx && n > (int64_t)num_views * ((int64_t)width * height)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;                       // an empty batch may come with NULL operands
+    if (!cams || !origins || !dirs || (sums && (!rgb || !mask))) return SHACIRA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(cams) & 15u) != 0 || (reinterpret_cast<uintptr_t>(jitter) & 7u) != 0) return SHACIRA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(sums) & 1u) != 0) return SHACIRA_EINVAL;
+    return (int)raygen_sums_dispatch(cams, num_views, width, height, view_idx, pixel_idx, jitter, n, sums, channels, mip,
+                                     bg_mode == SHACIRA_RAYGEN_BG_BLACK, origins, dirs, rgb, mask, (hipStream_t)stream);
+}
+
+// ---- mip levels of uint8 images ------------------------------------------------------------------------------------------------
+int shacira_image_mip(const uint8_t *images, int64_t num_views, int64_t height, int64_t width, int channels, int mip,
+                      uint16_t *sums, void *stream) {
+    if (mip < 1 || mip > SHACIRA_IMAGE_MIP_MAX || channels < 1 || channels > 4) return SHACIRA_EINVAL;
+    if (num_views <= 0 || height <= 0 || width <= 0) return SHACIRA_EINVAL;
+    const int64_t f = (int64_t)1 << mip;
+    if (height % f != 0 || width % f != 0) return SHACIRA_EINVAL;
+    // (H >> mip) * (W >> mip) < 2^31: a level's pixel indices are int32 (shacira_raygen_sums); no overflow, each factor < 2^63
+    if ((height >> mip) > INT32_MAX / (width >> mip)) return SHACIRA_EINVAL;
+    // every byte offset stays inside int64
+    if (num_views > INT64_MAX / 8 / height / width) return SHACIRA_EINVAL;
+    if (!images || !sums || (reinterpret_cast<uintptr_t>(sums) & 1u) != 0) return SHACIRA_EINVAL;
+    return (int)image_mip_dispatch(images, num_views, height, width, channels, mip, sums, (hipStream_t)stream);
+}
+
 // ---- pixel batches and the pixel loss ------------------------------------------------------------------------------------------
 // the operands the three calls share: the image's size, the index form and the range
 static bool pixel_args_ok(int64_t height, int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n) {

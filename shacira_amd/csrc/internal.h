@@ -201,6 +201,14 @@ hipError_t posenc_backward2_dispatch(int64_t n, int d, int F, int I, int P, cons
 hipError_t raygen_dispatch(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
                            const int32_t *pixel_idx, const float *jitter, int64_t n, const uint8_t *images, int channels,
                            bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s);
+// the same with the colours of a mip level: sums uint16 [V, H, W, channels], each the sum of 4^mip bytes
+hipError_t raygen_sums_dispatch(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                                const int32_t *pixel_idx, const float *jitter, int64_t n, const uint16_t *sums, int channels,
+                                int mip, bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s);
+
+// image_mip.hip: the uint16 block sums of one mip level of uint8 images (arguments checked by the entry point)
+hipError_t image_mip_dispatch(const uint8_t *images, int64_t num_views, int64_t height, int64_t width, int channels, int mip,
+                              uint16_t *sums, hipStream_t s);
 
 // shade.hip: the offline renderer's per-pixel passes (arguments checked by the entry points; mm_host may be NULL, light_host not)
 hipError_t shade_view_dispatch(int64_t n, int mode, float *normal, const float *dirs, const uint8_t *hit, const float *mm_host,

@@ -1,8 +1,10 @@
-// raygen.hip -- rays and target colours of (view, pixel) pairs from per-camera records and the uint8 training images (contract in
-// include/shacira_hip.h, shacira_raygen). One lane makes one ray:
+// raygen.hip -- rays and target colours of (view, pixel) pairs from per-camera records and the training images: their uint8 bytes
+// (shacira_raygen) or the uint16 block sums of a mip level (shacira_raygen_sums, made by image_mip.hip); contracts in
+// include/shacira_hip.h. The two differ in the pixel source only -- BytePixels / SumPixels below, which hand the body a pixel's
+// integers and their divisor -- and share every other line. One lane makes one ray:
 //   reads    its two indices (or derives them from the ray number in the whole-view form), its jitter pair, the camera's record
 //            (SHACIRA_RAYGEN_RECORD_FLOATS floats = five 16-byte loads; V records are a few KiB and stay in cache) and the
-//            pixel's 3 or 4 bytes;
+//            pixel's 3 or 4 bytes (6 or 8 bytes of sums);
 //   writes   three floats each into origins, dirs and rgb, and one mask byte. Lane i stores at base + 12 i, so a wavefront's
 //            64 lanes cover one contiguous run of 768 bytes per output: whole cache lines from one instruction whenever n is
 //            large, whatever the order of the indices. No LDS, no atomics, no workspace: two calls give the same bits.
@@ -25,16 +27,62 @@ struct Float3 {      // 12 bytes, 4-byte aligned: stored as one dwordx3
     float x, y, z;
 };
 
+// The pixel sources. load() yields the pixel's integers (b3 = full() without an alpha channel); a colour is the correctly rounded
+// (float)b / (float)full().
+struct BytePixels {                                   // uint8 [V, H, W, channels]
+    const uint8_t *base;
+    int channels, wide;                               // wide: 4 channels on a 4-byte aligned base, one load
+    __device__ __forceinline__ bool present() const { return base != nullptr; }
+    __device__ __forceinline__ float full() const { return 255.0f; }
+    __device__ __forceinline__ void load(int64_t pixel, uint32_t &b0, uint32_t &b1, uint32_t &b2, uint32_t &b3) const {
+        const uint8_t *p = base + pixel * channels;
+        b3 = 255u;
+        if (wide) {
+            const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
+            b0 = w & 255u;
+            b1 = (w >> 8) & 255u;
+            b2 = (w >> 16) & 255u;
+            b3 = w >> 24;
+        } else {
+            b0 = p[0];
+            b1 = p[1];
+            b2 = p[2];
+            if (channels == 4) b3 = p[3];
+        }
+    }
+};
+
+struct SumPixels {                                    // uint16 [V, H, W, channels]: sums of 4^mip bytes each
+    const uint16_t *base;
+    int channels, wide;                               // wide: 4 channels on an 8-byte aligned base, one load
+    uint32_t denom;                                   // 255 << (2 mip) <= 65280: exact in fp32
+    __device__ __forceinline__ bool present() const { return base != nullptr; }
+    __device__ __forceinline__ float full() const { return (float)denom; }
+    __device__ __forceinline__ void load(int64_t pixel, uint32_t &b0, uint32_t &b1, uint32_t &b2, uint32_t &b3) const {
+        const uint16_t *p = base + pixel * channels;
+        b3 = denom;
+        if (wide) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(p);
+            b0 = w.x & 0xFFFFu;
+            b1 = w.x >> 16;
+            b2 = w.y & 0xFFFFu;
+            b3 = w.y >> 16;
+        } else {
+            b0 = p[0];
+            b1 = p[1];
+            b2 = p[2];
+            if (channels == 4) b3 = p[3];
+        }
+    }
+};
+
 // kWhole: ray i is pixel i mod HW of view i div HW; otherwise the indices come from view_idx / pixel_idx
-template <bool kWhole>
-__global__ void __launch_bounds__(kRaygenBlock) raygen_kernel(const float4 *__restrict__ cams, int num_views, int width, int height,
-                                                              const int32_t *__restrict__ view_idx,
-                                                              const int32_t *__restrict__ pixel_idx,
-                                                              const float2 *__restrict__ jitter, int64_t n,
-                                                              const uint8_t *__restrict__ images, int channels, int bg_black,
-                                                              int word_loads, Float3 *__restrict__ origins,
-                                                              Float3 *__restrict__ dirs, Float3 *__restrict__ rgb,
-                                                              uint8_t *__restrict__ mask) {
+template <bool kWhole, class Pixels>
+__device__ __forceinline__ void make_rays(const float4 *__restrict__ cams, int num_views, int width, int height,
+                                          const int32_t *__restrict__ view_idx, const int32_t *__restrict__ pixel_idx,
+                                          const float2 *__restrict__ jitter, int64_t n, const Pixels images, int bg_black,
+                                          Float3 *__restrict__ origins, Float3 *__restrict__ dirs, Float3 *__restrict__ rgb,
+                                          uint8_t *__restrict__ mask) {
     const int64_t hw = (int64_t)width * height;       // < 2^31, checked by the entry point
     const float nan = __builtin_nanf("");
     for (int64_t i = (int64_t)blockIdx.x * kRaygenBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRaygenBlock) {
@@ -55,7 +103,7 @@ __global__ void __launch_bounds__(kRaygenBlock) raygen_kernel(const float4 *__re
             const Float3 bad = {nan, nan, nan};
             origins[i] = bad;
             dirs[i] = bad;
-            if (images) {
+            if (images.present()) {
                 rgb[i] = bad;
                 mask[i] = 0;
             }
@@ -99,25 +147,15 @@ __global__ void __launch_bounds__(kRaygenBlock) raygen_kernel(const float4 *__re
         const Float3 d = {wx / norm, wy / norm, wz / norm};
         origins[i] = o;
         dirs[i] = d;
-        if (images) {
-            const uint8_t *p = images + (view * hw + pixel) * channels;
-            uint32_t b0, b1, b2, b3 = 255u;
-            if (word_loads) {                         // 4 channels on a 4-byte aligned base: one load
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
-                b0 = w & 255u;
-                b1 = (w >> 8) & 255u;
-                b2 = (w >> 16) & 255u;
-                b3 = w >> 24;
-            } else {
-                b0 = p[0];
-                b1 = p[1];
-                b2 = p[2];
-                if (channels == 4) b3 = p[3];
-            }
-            Float3 c = {(float)b0 / 255.0f, (float)b1 / 255.0f, (float)b2 / 255.0f};
+        if (images.present()) {
+            const int channels = images.channels;
+            const float full = images.full();
+            uint32_t b0, b1, b2, b3;
+            images.load(view * hw + pixel, b0, b1, b2, b3);
+            Float3 c = {(float)b0 / full, (float)b1 / full, (float)b2 / full};
             uint8_t m = 1;
             if (channels == 4) {
-                const float a = (float)b3 / 255.0f;
+                const float a = (float)b3 / full;
                 const float rest = 1.0f - a;
                 if (bg_black) {
                     c.x = c.x - rest;
@@ -139,6 +177,33 @@ __global__ void __launch_bounds__(kRaygenBlock) raygen_kernel(const float4 *__re
     }
 }
 
+template <bool kWhole>
+__global__ void __launch_bounds__(kRaygenBlock) raygen_kernel(const float4 *__restrict__ cams, int num_views, int width, int height,
+                                                              const int32_t *__restrict__ view_idx,
+                                                              const int32_t *__restrict__ pixel_idx,
+                                                              const float2 *__restrict__ jitter, int64_t n,
+                                                              const uint8_t *__restrict__ images, int channels, int bg_black,
+                                                              int word_loads, Float3 *__restrict__ origins,
+                                                              Float3 *__restrict__ dirs, Float3 *__restrict__ rgb,
+                                                              uint8_t *__restrict__ mask) {
+    make_rays<kWhole>(cams, num_views, width, height, view_idx, pixel_idx, jitter, n, BytePixels{images, channels, word_loads},
+                      bg_black, origins, dirs, rgb, mask);
+}
+
+// the same rays with colours from a mip level's sums
+template <bool kWhole>
+__global__ void __launch_bounds__(kRaygenBlock) raysums_kernel(const float4 *__restrict__ cams, int num_views, int width, int height,
+                                                               const int32_t *__restrict__ view_idx,
+                                                               const int32_t *__restrict__ pixel_idx,
+                                                               const float2 *__restrict__ jitter, int64_t n,
+                                                               const uint16_t *__restrict__ sums, int channels, uint32_t denom,
+                                                               int bg_black, int wide, Float3 *__restrict__ origins,
+                                                               Float3 *__restrict__ dirs, Float3 *__restrict__ rgb,
+                                                               uint8_t *__restrict__ mask) {
+    make_rays<kWhole>(cams, num_views, width, height, view_idx, pixel_idx, jitter, n, SumPixels{sums, channels, wide, denom},
+                      bg_black, origins, dirs, rgb, mask);
+}
+
 }  // namespace
 
 hipError_t raygen_dispatch(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
@@ -156,6 +221,26 @@ hipError_t raygen_dispatch(const float *cams, int num_views, int width, int heig
         hipLaunchKernelGGL(raygen_kernel<true>, grid, dim3(kRaygenBlock), 0, s, reinterpret_cast<const float4 *>(cams), num_views,
                            width, height, view_idx, pixel_idx, reinterpret_cast<const float2 *>(jitter), n, images, channels,
                            (int)bg_black, word_loads, reinterpret_cast<Float3 *>(origins), reinterpret_cast<Float3 *>(dirs),
+                           reinterpret_cast<Float3 *>(rgb), mask);
+    return hipGetLastError();
+}
+
+hipError_t raygen_sums_dispatch(const float *cams, int num_views, int width, int height, const int32_t *view_idx,
+                                const int32_t *pixel_idx, const float *jitter, int64_t n, const uint16_t *sums, int channels,
+                                int mip, bool bg_black, float *origins, float *dirs, float *rgb, uint8_t *mask, hipStream_t s) {
+    const int64_t blocks = (n + kRaygenBlock - 1) / kRaygenBlock;
+    const dim3 grid((uint32_t)(blocks < kRaygenMaxGrid ? blocks : kRaygenMaxGrid));
+    const int wide = sums && channels == 4 && (reinterpret_cast<uintptr_t>(sums) & 7u) == 0;
+    const uint32_t denom = 255u << (2 * mip);
+    if (view_idx)
+        hipLaunchKernelGGL(raysums_kernel<false>, grid, dim3(kRaygenBlock), 0, s, reinterpret_cast<const float4 *>(cams), num_views,
+                           width, height, view_idx, pixel_idx, reinterpret_cast<const float2 *>(jitter), n, sums, channels, denom,
+                           (int)bg_black, wide, reinterpret_cast<Float3 *>(origins), reinterpret_cast<Float3 *>(dirs),
+                           reinterpret_cast<Float3 *>(rgb), mask);
+    else
+        hipLaunchKernelGGL(raysums_kernel<true>, grid, dim3(kRaygenBlock), 0, s, reinterpret_cast<const float4 *>(cams), num_views,
+                           width, height, view_idx, pixel_idx, reinterpret_cast<const float2 *>(jitter), n, sums, channels, denom,
+                           (int)bg_black, wide, reinterpret_cast<Float3 *>(origins), reinterpret_cast<Float3 *>(dirs),
                            reinterpret_cast<Float3 *>(rgb), mask);
     return hipGetLastError();
 }

@@ -1381,14 +1381,53 @@ def posenc_backward2(gg, row, grad_out, bands, d, include_input=True, prefix_wid
 
 
 # ---- ray generation (include/shacira_hip.h, shacira_raygen) ---------------------------------------------------------------------
-def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white", num_rays=None):
+def image_mip(images, mip, out=None):
+    """The mip level ``mip`` (1 .. 4) of uint8 images [V, H, W, C] or of one image [H, W, C] (C 1 .. 4) on the device, as exact
+    block sums in one kernel: uint16 [V, H >> mip, W >> mip, C] (or [H >> mip, W >> mip, C]), each the sum of a 2^mip x 2^mip
+    block of bytes; the block mean -- OpenCV's INTER_AREA -- is ``sum / 4^mip``. H and W must be multiples of 2^mip. ``out``: a
+    contiguous uint16 tensor of that shape to write into (a slice of a larger set, say)."""
+    _need_gpu(images)
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4):
+        raise RuntimeError(f"shacira_amd: image_mip expects uint8 images [V, H, W, C] or [H, W, C], got {images.dtype} "
+                           f"{tuple(images.shape)}")
+    single = images.dim() == 3
+    if single:
+        images = images.unsqueeze(0)
+    images = images.contiguous()
+    V, H, W, C = (int(s) for s in images.shape)
+    mip = int(mip)
+    if not 1 <= mip <= _lib.IMAGE_MIP_MAX:
+        raise RuntimeError(f"shacira_amd: image_mip takes mip 1..{_lib.IMAGE_MIP_MAX}, got {mip}")
+    if H % (1 << mip) or W % (1 << mip):
+        raise RuntimeError(f"shacira_amd: image_mip needs H and W divisible by {1 << mip} at mip {mip}, got {H} x {W}")
+    shape = (V, H >> mip, W >> mip, C)
+    if out is None:
+        sums = torch.empty(shape, dtype=torch.uint16, device=images.device)
+    else:
+        sums = out.unsqueeze(0) if single and out.dim() == 3 else out
+        if sums.dtype != torch.uint16 or tuple(sums.shape) != shape or sums.device != images.device or not sums.is_contiguous():
+            raise RuntimeError(f"shacira_amd: image_mip out must be contiguous uint16 {list(shape)} on {images.device}")
+    if sums.numel() > 0:
+        with _on_device(images.device):
+            rc = _lib.lib().shacira_image_mip(_ptr(images), V, H, W, C, mip, _ptr(sums), _stream(images))
+        _lib.check(rc, "image_mip")
+    return sums[0] if single else sums
+
+
+def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white", num_rays=None,
+           mip=0):
     """(origins, dirs, rgb, mask) of (view, pixel) pairs in one kernel: fp32 [n, 3] each and bool [n, 1]; ``rgb`` and ``mask``
     are None without ``images``. ``records``: fp32 [V, RAYGEN_RECORD_FLOATS] camera records; ``view_idx`` / ``pixel_idx``: int32
     [n] (pixel = y * W + x), or both None for the whole-view form -- ray i is pixel i mod (H W) of view i div (H W), for the first
     ``num_rays`` rays (default: all V H W); ``jitter``: fp32 [n, 2] or None; ``images``: uint8 [V, H, W, 3 or 4] or None.
-    An index out of range gives a NaN row and mask 0. Not differentiable."""
+    With ``mip`` > 0 ``images`` are the uint16 block sums of that mip level (``image_mip``), ``width`` and ``height`` the
+    level's, and a colour is sum / (255 * 4^mip). An index out of range gives a NaN row and mask 0. Not differentiable."""
     _need_gpu(records, view_idx, pixel_idx, jitter, images)
     dev = records.device
+    mip = int(mip or 0)
+    if not 0 <= mip <= _lib.IMAGE_MIP_MAX:
+        raise RuntimeError(f"shacira_amd: raygen takes mip 0..{_lib.IMAGE_MIP_MAX}, got {mip}")
+    pixel_dtype = torch.uint16 if mip > 0 else torch.uint8
     K = _lib.RAYGEN_RECORD_FLOATS
     if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != K or not records.is_contiguous():
         raise RuntimeError(f"shacira_amd: raygen expects contiguous fp32 records [V, {K}], got {records.dtype} "
@@ -1415,8 +1454,9 @@ def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, i
         jitter = jitter.detach().contiguous()
     channels = 4
     if images is not None:
-        if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[:3]) != (V, H, W) or images.device != dev:
-            raise RuntimeError(f"shacira_amd: raygen expects uint8 images [{V}, {H}, {W}, C] on {dev}, got {images.dtype} "
+        if images.dtype != pixel_dtype or images.dim() != 4 or tuple(images.shape[:3]) != (V, H, W) or images.device != dev:
+            what = f"uint16 sums (mip {mip})" if mip > 0 else "uint8 images"
+            raise RuntimeError(f"shacira_amd: raygen expects {what} [{V}, {H}, {W}, C] on {dev}, got {images.dtype} "
                                f"{tuple(images.shape)} on {images.device}")
         images = images.contiguous()
         channels = images.shape[3]
@@ -1426,10 +1466,16 @@ def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, i
     if images is not None:
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
         mask = torch.empty((n, 1), dtype=torch.bool, device=dev)
+    bg = _lib.RAYGEN_BG_BLACK if bg_color == "black" else _lib.RAYGEN_BG_WHITE
     with _on_device(dev):
-        rc = _lib.lib().shacira_raygen(_ptr(records), V, W, H, _ptr(view_idx), _ptr(pixel_idx), _ptr(jitter), n, _ptr(images),
-                                       channels, _lib.RAYGEN_BG_BLACK if bg_color == "black" else _lib.RAYGEN_BG_WHITE,
-                                       _ptr(origins), _ptr(dirs), _ptr(rgb), _ptr(mask), _stream(records))
+        if mip > 0:
+            rc = _lib.lib().shacira_raygen_sums(_ptr(records), V, W, H, _ptr(view_idx), _ptr(pixel_idx), _ptr(jitter), n,
+                                                _ptr(images), channels, mip, bg, _ptr(origins), _ptr(dirs), _ptr(rgb),
+                                                _ptr(mask), _stream(records))
+        else:
+            rc = _lib.lib().shacira_raygen(_ptr(records), V, W, H, _ptr(view_idx), _ptr(pixel_idx), _ptr(jitter), n,
+                                           _ptr(images), channels, bg, _ptr(origins), _ptr(dirs), _ptr(rgb), _ptr(mask),
+                                           _stream(records))
     _lib.check(rc, "raygen")
     return origins, dirs, rgb, mask
 

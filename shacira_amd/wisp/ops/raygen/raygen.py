@@ -77,12 +77,27 @@ def _camera_rays(cameras, view, px, py):
     return origins, dirs
 
 
-def composite_colors(pixels, bg_color="white"):
+def image_mip_torch(images, mip):
+    """``hip_ops.image_mip`` as torch operators, on whatever device the images live: uint8 [..., H, W, C] -> the exact sums of
+    the 2^mip x 2^mip blocks, int32 [..., H >> mip, W >> mip, C] (int32 because torch has few operators for uint16; every sum
+    fits 16 bits for mip <= 4)."""
+    f = 1 << int(mip)
+    *lead, H, W, C = images.shape
+    if H % f or W % f:
+        raise ValueError(f"image_mip_torch: {H} x {W} is not divisible by 2^mip = {f}")
+    return images.reshape(*lead, H // f, f, W // f, f, C).to(torch.int32).sum(dim=(-4, -2), dtype=torch.int32)
+
+
+def composite_colors(pixels, bg_color="white", mip=0):
     """uint8 pixels [n, 3 or 4] -> (rgb fp32 [n, 3], mask bool [n, 1]) by the reference's fp32 chain (wisp/ops/image/io.py:106,
-    nerf_standard_dataset.py:415-428)."""
+    nerf_standard_dataset.py:415-428). With ``mip`` > 0 the pixels are a mip level's integer block sums (uint16 or any wider
+    integer type) and the divisor is 255 * 4^mip: the correctly rounded block mean."""
     # by a TENSOR 255: on the device torch turns a division by a Python scalar into a product with 1 / 255, which is not the
     # correctly rounded quotient the host (where the reference converts its images) and the kernel compute
-    img = pixels.to(torch.float32) / torch.full((1,), 255.0, dtype=torch.float32, device=pixels.device)
+    full = 255.0 * 4 ** int(mip or 0)
+    if pixels.dtype == torch.uint16:
+        pixels = pixels.to(torch.int32)
+    img = pixels.to(torch.float32) / torch.full((1,), full, dtype=torch.float32, device=pixels.device)
     rgb, alpha = img[..., :3], img[..., 3:4]
     if alpha.numel() == 0 and img.shape[-1] == 3:
         return rgb.contiguous(), torch.ones_like(rgb[..., 0:1]).bool()
@@ -95,24 +110,25 @@ def composite_colors(pixels, bg_color="white"):
     return rgb.clamp(0.0, 1.0), mask
 
 
-def generate_rays(cameras, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white"):
+def generate_rays(cameras, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white", mip=0):
     """(Rays, rgb, mask) of the pixels ``pixel_idx`` (y * W + x) of the views ``view_idx`` of ``cameras`` (one Camera of V views):
     fp32 origins and unit directions [n, 3], and -- with ``images`` uint8 [V, H, W, 3 or 4] -- the target colours composited over
     ``bg_color`` [n, 3] and the alpha mask [n, 1]; both None without images. Both indices None: every pixel of every view, view
-    by view. ``jitter`` [n, 2]: a sub-pixel offset (jx, jy) added to the pixel centres. Device tensors run the fused kernel, where
-    an index out of range yields a NaN ray; host tensors run the composite in the camera's dtype."""
+    by view. ``jitter`` [n, 2]: a sub-pixel offset (jx, jy) added to the pixel centres. ``mip`` > 0: ``images`` are the uint16
+    block sums of that mip level and the cameras have the level's size. Device tensors run the fused kernel, where an index out
+    of range yields a NaN ray; host tensors run the composite in the camera's dtype."""
     if bg_color not in ("white", "black"):
         raise ValueError(f"bg_color must be 'white' or 'black', got {bg_color!r}")
     if cameras.device.type == "cuda":
         W, H = cameras.width, cameras.height
         as_i32 = lambda t: None if t is None else t.to(device=cameras.device, dtype=torch.int32)
         origins, dirs, rgb, mask = hip_ops.raygen(camera_records(cameras), W, H, as_i32(view_idx), as_i32(pixel_idx), jitter,
-                                                  images, bg_color)
+                                                  images, bg_color, mip=mip)
         return Rays(origins, dirs, dist_min=cameras.near, dist_max=cameras.far), rgb, mask
-    return composite_rays(cameras, view_idx, pixel_idx, jitter, images, bg_color)
+    return composite_rays(cameras, view_idx, pixel_idx, jitter, images, bg_color, mip=mip)
 
 
-def composite_rays(cameras, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white"):
+def composite_rays(cameras, view_idx=None, pixel_idx=None, jitter=None, images=None, bg_color="white", mip=0):
     """``generate_rays`` as a chain of torch operators in the camera's dtype, on whatever device the camera lives: the host path,
     and the yardstick the kernel is measured against (tools/raygen_ab.py)."""
     W, H, dev = cameras.width, cameras.height, cameras.device
@@ -127,7 +143,9 @@ def composite_rays(cameras, view_idx=None, pixel_idx=None, jitter=None, images=N
     origins, dirs = _camera_rays(cameras, view_idx, px, py)
     rgb = mask = None
     if images is not None:
-        rgb, mask = composite_colors(images.reshape(len(cameras), H * W, -1)[view_idx, pixel_idx], bg_color)
+        if images.dtype == torch.uint16:                 # torch does not index uint16
+            images = images.to(torch.int32)
+        rgb, mask = composite_colors(images.reshape(len(cameras), H * W, -1)[view_idx, pixel_idx], bg_color, mip)
     rays = Rays(origins.to(torch.float32), dirs.to(torch.float32), dist_min=cameras.near, dist_max=cameras.far)
     return rays, rgb, mask
 
