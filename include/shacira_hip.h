@@ -843,6 +843,85 @@ SHACIRA_API int shacira_raygen_sums(const float *cams, int num_views, int width,
                                     uint8_t *mask, void *stream);
 
 /*
+ * Structured point clouds (ABI 11, additive): a coloured structured point cloud (SPC) built from depth images or from a point
+ * cloud, and its first-hit tracer -- the reference's RGB-D path (wisp/datasets/formats/rtmv_dataset.py, wisp/ops/pointcloud,
+ * wisp/models/nefs/spc_field.py, wisp/tracers/packed_spc_tracer.py) from the data that stay on the device: the uint8 images (or
+ * a mip level's uint16 sums), one fp32 depth plane and the camera records of shacira_raygen.
+ *
+ * Device layout of an SPC of level L, 1 <= L <= SHACIRA_OCTREE_MAX_LEVEL, G = 2^L:
+ *   words    int32 [shacira_spc_num_words(L) = max(1, G^3 / 32)]: cell (x, y, z) has key (x G + y) G + z and is bit key & 31 of
+ *            word key >> 5 -- the layout of OctreeAS.packed_occupancy and shacira_mesh_voxelize; unused bits are 0
+ *   rank     int32 [same length]: the number of set bits in all earlier words (an exclusive prefix), so that
+ *            slot(key) = rank[key >> 5] + popc(words[key >> 5] & ((1u << (key & 31)) - 1)) numbers the cells in key order
+ *   colors   uint8 [cells, 4]: RGBA by slot, A = 255
+ *
+ * The depth entries share (cams, num_views, width, height) of shacira_raygen (num_views may be 0: nothing to do) and
+ *   depth    fp32 [num_views, H, W]. A pixel is VALID iff its depth is finite.
+ * The POINT of a valid pixel (v, y, x): shacira_raygen's origin o and unit direction d of that pixel without jitter, then
+ *     s_i = d_i * depth (one rounding)     p_i = o_i + s_i (one rounding)     -- no fused multiply-add.
+ * The COLOUR of a pixel: shacira_raygen's (mip 0: images uint8) or shacira_raygen_sums' (mip 1 .. 4: images are the uint16 sums,
+ * width and height the level's) composited fp32 colour c over bg_mode, quantised q = (uint8) rintf(255 * c).
+ * The CELL of a point at level L (OctreeAS.quantize_pointcloud): per axis floorf((x + 1) * 0.5f * G); a point with a cell that is
+ * not finite is dropped, every other cell is clamped to 0 .. G - 1 (x = 1 falls into the last cell).
+ *
+ * shacira_depth_bounds         bounds fp32 [6] = min x, y, z, max x, y, z of the points of all valid pixels, count int64 [1] =
+ *                              their number; both are initialised by the call, on the stream. No valid pixel: +inf, -inf, 0. Min
+ *                              and max are taken with integer atomics on an order-preserving image of the floats: the result does
+ *                              not depend on the order, two calls return the same bits.
+ * shacira_depth_points_count   block_counts int32 [ceil(V H W / 256)]: the valid pixels among each 256 consecutive ones
+ * shacira_depth_points_emit    the compacted cloud in (view, pixel) order: points fp32 [M, 3] and, when rgb != NULL, the colour
+ *                              bytes uint8 [M, 3] (images, channels, mip, bg_mode are then required; ignored otherwise).
+ *                              block_offsets int64 [blocks] is the caller's exclusive scan of block_counts. Two calls return the
+ *                              same bits.
+ * shacira_spc_mark_points      ORs the bit of the cell of every point of points fp32 [n, 3] into `words`, which the caller zeroed
+ * shacira_spc_mark_depth       the same for the points of the valid pixels; the cloud is never materialised
+ * shacira_spc_rank             rank[w] = popc(words[w]) for every word: the caller's exclusive scan (integers: exact) turns it
+ *                              into `rank`, and the inclusive total is the cell count -- on the device, no read-back here
+ * shacira_spc_accumulate_points / _depth    adds (q_R, q_G, q_B, 1) into sums uint64 [cells, 4] (zeroed by the caller) at the slot
+ *                              of the point's cell, with 64-bit integer atomics: exact, so independent of the order. _points
+ *                              takes the bytes rgb uint8 [n, 3]. A point whose cell is not set in `words`, or whose slot is
+ *                              outside [0, cells), adds nothing.
+ * shacira_spc_resolve          colors[slot, c] = (2 sum_c + n) / (2 n) by integer division (the mean rounded to nearest, ties
+ *                              up), A = 255; a slot with n = 0 gets (0, 0, 0, 255)
+ * shacira_spc_first_hit        origins, dirs fp32 [num_rays, 3]; colors may be NULL (rank and rgb are then not read / written).
+ *                              One lane per ray writes depth fp32 [N], hit uint8 [N], pidx int32 [N] (the Morton index of the
+ *                              cell, x most significant, as shacira_raytrace_dense_emit writes it) and rgb fp32 [N, 3] =
+ *                              byte / 255. A miss writes 0 / 0 / -1 / (0, 0, 0). A ray with a component of its origin or
+ *                              direction that is not finite is a miss, tested before anything else. Every other ray gets the
+ *                              FIRST nugget shacira_raytrace_dense_emit writes for it on the same occupied set: the same pidx,
+ *                              and its entry depth bit for bit -- the walk is that kernel's arithmetic (slab test, tmax += tdelta,
+ *                              tie order x, y, z), only the occupancy is read from the packed words.
+ * Validation precedes any HIP call and returns SHACIRA_EINVAL: a negative count, width or height <= 0, W H >= 2^31, more than
+ * 2^31 - 1 workgroups of 256 pixels, level outside 1 .. 10, channels outside {3, 4}, mip outside 0 .. 4 or an unknown bg_mode
+ * where colours are made, num_rays >= 2^31, a NULL or misaligned operand (cams 16 bytes, sums and count 8, words / rank / colors
+ * / floats 4, uint16 images 2). n == 0 (no view, no point, no ray, no cell) returns 0 with nothing enqueued. Every entry runs on
+ * `stream`, allocates nothing and never synchronises with the host.
+ */
+SHACIRA_API size_t shacira_spc_num_words(int level);
+SHACIRA_API int shacira_depth_bounds(const float *cams, int num_views, int width, int height, const float *depth, float *bounds,
+                                     int64_t *count, void *stream);
+SHACIRA_API int shacira_depth_points_count(const float *cams, int num_views, int width, int height, const float *depth,
+                                           int32_t *block_counts, void *stream);
+SHACIRA_API int shacira_depth_points_emit(const float *cams, int num_views, int width, int height, const float *depth,
+                                          const void *images, int channels, int mip, int bg_mode, const int64_t *block_offsets,
+                                          float *points, uint8_t *rgb, void *stream);
+SHACIRA_API int shacira_spc_mark_points(int64_t n, const float *points, int level, uint32_t *words, void *stream);
+SHACIRA_API int shacira_spc_mark_depth(const float *cams, int num_views, int width, int height, const float *depth, int level,
+                                       uint32_t *words, void *stream);
+SHACIRA_API int shacira_spc_rank(int level, const uint32_t *words, int32_t *rank, void *stream);
+SHACIRA_API int shacira_spc_accumulate_points(int64_t n, const float *points, const uint8_t *rgb, int level,
+                                              const uint32_t *words, const int32_t *rank, int64_t cells, uint64_t *sums,
+                                              void *stream);
+SHACIRA_API int shacira_spc_accumulate_depth(const float *cams, int num_views, int width, int height, const float *depth,
+                                             const void *images, int channels, int mip, int bg_mode, int level,
+                                             const uint32_t *words, const int32_t *rank, int64_t cells, uint64_t *sums,
+                                             void *stream);
+SHACIRA_API int shacira_spc_resolve(int64_t cells, const uint64_t *sums, uint8_t *colors, void *stream);
+SHACIRA_API int shacira_spc_first_hit(int64_t num_rays, const float *origins, const float *dirs, int level,
+                                      const uint32_t *words, const int32_t *rank, const uint8_t *colors, float *depth,
+                                      uint8_t *hit, int32_t *pidx, float *rgb, void *stream);
+
+/*
  * Pixel batches and the pixel loss: an image fit's coordinates, target colours, squared error and "clamped PSNR" statistics made
  * from pixel indices and ONE uint8 image that stays on the device -- what wisp/datasets/formats/multi_image_dataset.py:140-161
  * stores per pixel (40 bytes on the host) and :190-242 gathers per batch, and what wisp/ops/image/metrics.py:39-58 computes from a

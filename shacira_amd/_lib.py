@@ -28,6 +28,7 @@ IMAGE_MIP_MAX = 4                                                       # SHACIR
 PIXEL_MAX_GRID, PIXEL_PARTIAL_BYTES = 2048, 24                          # SHACIRA_PIXEL_* of the header
 MESH_SAMPLE_SURFACE, MESH_SAMPLE_NEAR, MESH_SAMPLE_CUBE, MESH_SAMPLE_CELLS = 0, 1, 2, 3   # SHACIRA_MESH_SAMPLE_* of the header
 MESH_SAMPLE_BLOCK = 256
+DEPTH_POINTS_BLOCK = 256                                                # pixels per count of shacira_depth_points_count
 SHADE_RB, SHADE_NORMAL, SHADE_MATCAP, SHADE_MAX_TEX, SHADOW_BLUR_RADIUS = 0, 1, 2, 32768, 8   # SHACIRA_SHADE_* / _SHADOW_*
 
 _lock = threading.Lock()
@@ -87,6 +88,17 @@ SIGNATURES = {
     "shacira_raygen": (_i, [_p, _i, _i, _i, _p, _p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
     "shacira_image_mip": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _p]),
     "shacira_raygen_sums": (_i, [_p, _i, _i, _i, _p, _p, _p, _i64, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "shacira_spc_num_words": (_sz, [_i]),
+    "shacira_depth_bounds": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "shacira_depth_points_count": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "shacira_depth_points_emit": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "shacira_spc_mark_points": (_i, [_i64, _p, _i, _p, _p]),
+    "shacira_spc_mark_depth": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
+    "shacira_spc_rank": (_i, [_i, _p, _p, _p]),
+    "shacira_spc_accumulate_points": (_i, [_i64, _p, _p, _i, _p, _p, _i64, _p, _p]),
+    "shacira_spc_accumulate_depth": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i64, _p, _p]),
+    "shacira_spc_resolve": (_i, [_i64, _p, _p, _p]),
+    "shacira_spc_first_hit": (_i, [_i64, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "shacira_pixel_batch": (_i, [_p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p]),
     "shacira_pixel_loss_workspace_bytes": (_sz, [_i64]),
     "shacira_pixel_loss_forward": (_i, [_p, _i64, _p, _i64, _i64, _p, _i, _i64, _i64, _p, _p, _p, _sz, _p]),

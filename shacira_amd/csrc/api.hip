@@ -715,6 +715,135 @@ int shacira_image_mip(const uint8_t *images, int64_t num_views, int64_t height, 
     return (int)image_mip_dispatch(images, num_views, height, width, channels, mip, sums, (hipStream_t)stream);
 }
 
+// ---- structured point clouds ----------------------------------------------------------------------------------------------------
+// the operands the depth entries share; 0, or SHACIRA_EINVAL. With colours: the images and their form are checked too
+static int depth_args(const float *cams, int num_views, int width, int height, const float *depth, bool colours,
+                      const void *images, int channels, int mip, int bg_mode, DepthArgs &a) {
+    if (num_views < 0 || width <= 0 || height <= 0) return SHACIRA_EINVAL;
+    if ((int64_t)width * height > INT32_MAX) return SHACIRA_EINVAL;          // pixel indices are int32
+    // workgroups of 256 pixels are a grid dimension
+    if (num_views > 0 && (int64_t)width * height > ((int64_t)INT32_MAX * 256) / num_views) return SHACIRA_EINVAL;
+    if (colours) {
+        if (mip < 0 || mip > SHACIRA_IMAGE_MIP_MAX || (channels != 3 && channels != 4)) return SHACIRA_EINVAL;
+        if (bg_mode != SHACIRA_RAYGEN_BG_WHITE && bg_mode != SHACIRA_RAYGEN_BG_BLACK) return SHACIRA_EINVAL;
+    }
+    if (num_views > 0) {
+        if (!cams || !depth || (reinterpret_cast<uintptr_t>(cams) & 15u) != 0 || (reinterpret_cast<uintptr_t>(depth) & 3u) != 0)
+            return SHACIRA_EINVAL;
+        if (colours && (!images || (mip > 0 && (reinterpret_cast<uintptr_t>(images) & 1u) != 0))) return SHACIRA_EINVAL;
+    }
+    a = DepthArgs{cams, num_views, width, height, depth, colours ? images : nullptr, colours ? channels : 3, colours ? mip : 0,
+                  colours && bg_mode == SHACIRA_RAYGEN_BG_BLACK};
+    return 0;
+}
+
+static bool spc_level_ok(int level) { return level >= 1 && level <= SHACIRA_OCTREE_MAX_LEVEL; }
+static bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+size_t shacira_spc_num_words(int level) {
+    if (!spc_level_ok(level)) return 0;
+    const size_t cells = (size_t)1 << (3 * level);
+    return cells < 32 ? 1 : cells / 32;
+}
+
+int shacira_depth_bounds(const float *cams, int num_views, int width, int height, const float *depth, float *bounds,
+                         int64_t *count, void *stream) {
+    DepthArgs a;
+    const int rc = depth_args(cams, num_views, width, height, depth, false, nullptr, 0, 0, 0, a);
+    if (rc != 0) return rc;
+    if (num_views == 0) return 0;
+    if (!bounds || !count || !aligned4(bounds) || (reinterpret_cast<uintptr_t>(count) & 7u) != 0) return SHACIRA_EINVAL;
+    return (int)depth_bounds_dispatch(a, bounds, count, (hipStream_t)stream);
+}
+
+int shacira_depth_points_count(const float *cams, int num_views, int width, int height, const float *depth,
+                               int32_t *block_counts, void *stream) {
+    DepthArgs a;
+    const int rc = depth_args(cams, num_views, width, height, depth, false, nullptr, 0, 0, 0, a);
+    if (rc != 0) return rc;
+    if (num_views == 0) return 0;
+    if (!block_counts) return SHACIRA_EINVAL;
+    return (int)depth_points_dispatch(true, a, block_counts, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int shacira_depth_points_emit(const float *cams, int num_views, int width, int height, const float *depth, const void *images,
+                              int channels, int mip, int bg_mode, const int64_t *block_offsets, float *points, uint8_t *rgb,
+                              void *stream) {
+    DepthArgs a;
+    const int rc = depth_args(cams, num_views, width, height, depth, rgb != nullptr, images, channels, mip, bg_mode, a);
+    if (rc != 0) return rc;
+    if (num_views == 0) return 0;
+    if (!block_offsets || !points || !aligned4(points)) return SHACIRA_EINVAL;
+    return (int)depth_points_dispatch(false, a, nullptr, block_offsets, points, rgb, (hipStream_t)stream);
+}
+
+int shacira_spc_mark_points(int64_t n, const float *points, int level, uint32_t *words, void *stream) {
+    if (n < 0 || !spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (n == 0) return 0;
+    if (!points || !words || !aligned4(points) || !aligned4(words)) return SHACIRA_EINVAL;
+    return (int)spc_mark_points_dispatch(n, points, level, words, (hipStream_t)stream);
+}
+
+int shacira_spc_mark_depth(const float *cams, int num_views, int width, int height, const float *depth, int level,
+                           uint32_t *words, void *stream) {
+    DepthArgs a;
+    const int rc = depth_args(cams, num_views, width, height, depth, false, nullptr, 0, 0, 0, a);
+    if (rc != 0) return rc;
+    if (!spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (num_views == 0) return 0;
+    if (!words || !aligned4(words)) return SHACIRA_EINVAL;
+    return (int)spc_mark_depth_dispatch(a, level, words, (hipStream_t)stream);
+}
+
+int shacira_spc_rank(int level, const uint32_t *words, int32_t *rank, void *stream) {
+    if (!spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (!words || !rank || !aligned4(words) || !aligned4(rank)) return SHACIRA_EINVAL;
+    return (int)spc_popcount_dispatch((int64_t)shacira_spc_num_words(level), words, rank, (hipStream_t)stream);
+}
+
+int shacira_spc_accumulate_points(int64_t n, const float *points, const uint8_t *rgb, int level, const uint32_t *words,
+                                  const int32_t *rank, int64_t cells, uint64_t *sums, void *stream) {
+    if (n < 0 || cells < 0 || !spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (n == 0 || cells == 0) return 0;
+    if (!points || !rgb || !words || !rank || !sums) return SHACIRA_EINVAL;
+    if (!aligned4(points) || !aligned4(words) || !aligned4(rank) || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0)
+        return SHACIRA_EINVAL;
+    return (int)spc_accumulate_points_dispatch(n, points, rgb, level, words, rank, cells, sums, (hipStream_t)stream);
+}
+
+int shacira_spc_accumulate_depth(const float *cams, int num_views, int width, int height, const float *depth, const void *images,
+                                 int channels, int mip, int bg_mode, int level, const uint32_t *words, const int32_t *rank,
+                                 int64_t cells, uint64_t *sums, void *stream) {
+    DepthArgs a;
+    const int rc = depth_args(cams, num_views, width, height, depth, true, images, channels, mip, bg_mode, a);
+    if (rc != 0) return rc;
+    if (cells < 0 || !spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (num_views == 0 || cells == 0) return 0;
+    if (!words || !rank || !sums) return SHACIRA_EINVAL;
+    if (!aligned4(words) || !aligned4(rank) || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0) return SHACIRA_EINVAL;
+    return (int)spc_accumulate_depth_dispatch(a, level, words, rank, cells, sums, (hipStream_t)stream);
+}
+
+int shacira_spc_resolve(int64_t cells, const uint64_t *sums, uint8_t *colors, void *stream) {
+    if (cells < 0) return SHACIRA_EINVAL;
+    if (cells == 0) return 0;
+    if (!sums || !colors || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0 || !aligned4(colors)) return SHACIRA_EINVAL;
+    return (int)spc_resolve_dispatch(cells, sums, colors, (hipStream_t)stream);
+}
+
+int shacira_spc_first_hit(int64_t num_rays, const float *origins, const float *dirs, int level, const uint32_t *words,
+                          const int32_t *rank, const uint8_t *colors, float *depth, uint8_t *hit, int32_t *pidx, float *rgb,
+                          void *stream) {
+    if (num_rays < 0 || num_rays > INT32_MAX || !spc_level_ok(level)) return SHACIRA_EINVAL;
+    if (num_rays == 0) return 0;
+    if (!origins || !dirs || !words || !depth || !hit || !pidx || (colors && (!rank || !rgb))) return SHACIRA_EINVAL;
+    if (!aligned4(origins) || !aligned4(dirs) || !aligned4(words) || !aligned4(rank) || !aligned4(colors) || !aligned4(depth) ||
+        !aligned4(pidx) || !aligned4(rgb))
+        return SHACIRA_EINVAL;
+    return (int)spc_first_hit_dispatch(num_rays, origins, dirs, level, words, rank, colors, depth, hit, pidx, rgb,
+                                       (hipStream_t)stream);
+}
+
 // ---- pixel batches and the pixel loss ------------------------------------------------------------------------------------------
 // the operands the three calls share: the image's size, the index form and the range
 static bool pixel_args_ok(int64_t height, int64_t width, const void *pixel_idx, int idx_bits, int64_t start, int64_t n) {

@@ -210,6 +210,30 @@ hipError_t raygen_sums_dispatch(const float *cams, int num_views, int width, int
 hipError_t image_mip_dispatch(const uint8_t *images, int64_t num_views, int64_t height, int64_t width, int channels, int mip,
                               uint16_t *sums, hipStream_t s);
 
+// spc.hip: structured point clouds from depth images or point clouds, and their first-hit tracer (arguments checked by the entry
+// points). DepthArgs names the [V, H, W] pixels of a depth data set: by value in the kernel arguments
+struct DepthArgs {
+    const float *cams;            // [V, SHACIRA_RAYGEN_RECORD_FLOATS]
+    int32_t num_views, width, height;
+    const float *depth;           // [V, H, W], not finite = no point
+    const void *images;           // uint8 [V, H, W, channels] (mip 0) or uint16 sums (mip > 0), or NULL where no colour is made
+    int32_t channels, mip, bg_black;
+};
+hipError_t depth_bounds_dispatch(const DepthArgs &a, float *bounds, int64_t *count, hipStream_t s);
+hipError_t depth_points_dispatch(bool count, const DepthArgs &a, int32_t *block_counts, const int64_t *block_offsets,
+                                 float *points, uint8_t *rgb, hipStream_t s);
+hipError_t spc_mark_points_dispatch(int64_t n, const float *points, int level, uint32_t *words, hipStream_t s);
+hipError_t spc_mark_depth_dispatch(const DepthArgs &a, int level, uint32_t *words, hipStream_t s);
+hipError_t spc_popcount_dispatch(int64_t num_words, const uint32_t *words, int32_t *counts, hipStream_t s);
+hipError_t spc_accumulate_points_dispatch(int64_t n, const float *points, const uint8_t *rgb, int level, const uint32_t *words,
+                                          const int32_t *rank, int64_t cells, uint64_t *sums, hipStream_t s);
+hipError_t spc_accumulate_depth_dispatch(const DepthArgs &a, int level, const uint32_t *words, const int32_t *rank, int64_t cells,
+                                         uint64_t *sums, hipStream_t s);
+hipError_t spc_resolve_dispatch(int64_t cells, const uint64_t *sums, uint8_t *colors, hipStream_t s);
+hipError_t spc_first_hit_dispatch(int64_t num_rays, const float *origins, const float *dirs, int level, const uint32_t *words,
+                                  const int32_t *rank, const uint8_t *colors, float *depth, uint8_t *hit, int32_t *pidx,
+                                  float *rgb, hipStream_t s);
+
 // shade.hip: the offline renderer's per-pixel passes (arguments checked by the entry points; mm_host may be NULL, light_host not)
 hipError_t shade_view_dispatch(int64_t n, int mode, float *normal, const float *dirs, const uint8_t *hit, const float *mm_host,
                                const uint8_t *tex, int mh, int mw, int mc, float *rgb, float *uv_out, uint8_t *rgb8_out,

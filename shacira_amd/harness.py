@@ -1206,3 +1206,77 @@ def render_sdf(nef, out_dir=None, res=(256, 256), views=RENDER_SDF_VIEWS, shadin
     finally:
         nef.train(was_training)
     return out
+
+
+# ---- RGB-D scenes: an analytic RTMV data set and the structured point cloud rendered from it -------------------------------------
+ANALYTIC_RTMV_RADIUS = 0.5          # the sphere of write_analytic_rtmv, at the origin
+ANALYTIC_RTMV_DISTANCE = 3.0        # its cameras sit on the sphere of this radius
+
+
+def write_analytic_rtmv(path, views, height, width, seed=0):
+    """Write an RTMV-style data set into ``path``: per view ``NNNNN.json`` (look-at camera in Blender's z-up convention, focal
+    lengths in pixels), ``NNNNN.png`` (RGBA) and ``NNNNN.depth.npz`` (``arr_0`` fp32 [H, W, 1]). The scene is a sphere of radius
+    ``ANALYTIC_RTMV_RADIUS`` at the origin seen from ``views`` cameras on the sphere of radius ``ANALYTIC_RTMV_DISTANCE``. The
+    depth of a pixel is the fp64 distance to the sphere along this package's own fp32 unit ray through the pixel centre (the
+    host composite of ``wisp.ops.raygen``, with ``RTMVDataset``'s camera handling), stored as fp32; 1e10 where the ray misses.
+    The colour is 0.5 + p / (2 r) of the hit point p in the y-up world, alpha 255 on the object and 0 off it. Runs on the host.
+    Returns the list of json paths."""
+    import json
+    import os
+    import numpy as np
+    from PIL import Image
+    from .wisp.core import Camera, blender_coords
+    from .wisp.ops.raygen import generate_rays
+    gen = torch.Generator().manual_seed(seed)
+    eye = torch.randn(views, 3, generator=gen, dtype=torch.float64)
+    eye[:, 2] = eye[:, 2].abs() * 0.5 + 0.2                      # upper hemisphere, off the pole (z is up here)
+    eye = ANALYTIC_RTMV_DISTANCE * eye / eye.norm(dim=1, keepdim=True)
+    at, up = [0.0, 0.0, 0.0], [0.0, 0.0, 1.0]
+    focal = 0.5 * width / math.tan(0.25)
+    os.makedirs(path, exist_ok=True)
+    files = []
+    for i in range(views):
+        camera = Camera.from_args(eye=eye[i], at=torch.tensor(at, dtype=torch.float64), up=torch.tensor(up, dtype=torch.float64),
+                                  focal_x=focal, focal_y=focal, width=width, height=height, near=0.0, far=6.0)
+        camera.change_coordinate_system(blender_coords())
+        rays, _, _ = generate_rays(camera)
+        o, d = rays.origins.double(), rays.dirs.double()
+        b = (o * d).sum(-1)
+        disc = b * b - ((o * o).sum(-1) - ANALYTIC_RTMV_RADIUS ** 2)
+        hit = disc > 0
+        t = -b - torch.sqrt(disc.clamp_min(0.0))
+        p = o + d * t[:, None]
+        rgb = (0.5 + p / (2.0 * ANALYTIC_RTMV_RADIUS)).clamp(0.0, 1.0)
+        rgba = torch.cat([rgb, torch.ones_like(t)[:, None]], dim=-1) * hit[:, None]
+        rgba = (rgba * 255.0).round().to(torch.uint8).reshape(height, width, 4).numpy()
+        depth = torch.where(hit, t, torch.full_like(t, 1e10)).to(torch.float32).reshape(height, width, 1).numpy()
+        base = os.path.join(path, f"{i:05d}")
+        Image.fromarray(rgba, "RGBA").save(base + ".png")
+        np.savez(base + ".depth.npz", depth)
+        with open(base + ".json", "w") as fh:
+            json.dump(dict(camera_data=dict(camera_look_at=dict(eye=eye[i].tolist(), at=at, up=up), width=width, height=height,
+                                            intrinsics=dict(fx=focal, fy=focal))), fh, indent=1)
+        files.append(base + ".json")
+    return files
+
+
+def render_spc(dataset, level, out_dir=None):
+    """Look at the structured point cloud of an RGB-D data set: ``dataset.as_spc(level)`` as an ``SPCField``, every view of the
+    data set traced by ``PackedSPCTracer`` (one launch per view). Returns the [H, W, C] ``RenderBuffer`` s; with ``out_dir``
+    every view is also written as ``view{i}_rgb.png`` and ``view{i}_depth.png``."""
+    import os
+    from .wisp.models.nefs import SPCField
+    from .wisp.ops.image.io import write_png
+    from .wisp.tracers import PackedSPCTracer
+    nef, tracer = SPCField(dataset.as_spc(level)), PackedSPCTracer()
+    H, W = dataset.img_shape[:2]
+    out = []
+    for i in range(len(dataset)):
+        rb = tracer(nef, dataset[i]["rays"]).reshape(H, W, -1)
+        out.append(rb)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            img = rb.image().byte().cpu()
+            write_png(os.path.join(out_dir, f"view{i}_rgb.png"), img.rgb)
+            write_png(os.path.join(out_dir, f"view{i}_depth.png"), img.depth)
+    return out

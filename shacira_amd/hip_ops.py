@@ -1117,10 +1117,10 @@ def mesh_face_cdf(triangles):
     return torch.from_numpy(cdf.view(np.int32)).to(triangles.device)
 
 
-def _u32_operand(t, shape, dev, what):
+def _u32_operand(t, shape, dev, what, who="mesh_sample"):
     """``t`` as contiguous 32-bit integer words of ``shape`` on ``dev`` (int32 and uint32 tensors carry the same bits)."""
     if t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or t.device != dev or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"shacira_amd: mesh_sample expects {what} as int32 / uint32 {list(shape)} on {dev}, got {t.dtype} "
+        raise RuntimeError(f"shacira_amd: {who} expects {what} as int32 / uint32 {list(shape)} on {dev}, got {t.dtype} "
                            f"{tuple(t.shape)} on {t.device}")
     return t.contiguous()
 
@@ -1478,6 +1478,194 @@ def raygen(records, width, height, view_idx=None, pixel_idx=None, jitter=None, i
                                            _stream(records))
     _lib.check(rc, "raygen")
     return origins, dirs, rgb, mask
+
+
+# ---- structured point clouds (include/shacira_hip.h, shacira_depth_* / shacira_spc_*) ------------------------------------------
+def _depth_operands(records, depth, images=None, bg_color="white", mip=0):
+    """The checked operands the depth entries share: (records, depth, images, head) with ``head`` the leading C arguments
+    (cams, V, W, H, depth). ``depth``: fp32 [V, H, W]; ``images``: uint8 [V, H, W, 3 or 4], or the uint16 sums of ``mip``."""
+    _need_gpu(records, depth, images)
+    dev = records.device
+    K = _lib.RAYGEN_RECORD_FLOATS
+    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != K or not records.is_contiguous():
+        raise RuntimeError(f"shacira_amd: expected contiguous fp32 records [V, {K}], got {records.dtype} {tuple(records.shape)}")
+    V = records.shape[0]
+    if depth.dtype != torch.float32 or depth.dim() != 3 or depth.shape[0] != V or depth.device != dev:
+        raise RuntimeError(f"shacira_amd: expected fp32 depth [{V}, H, W] on {dev}, got {depth.dtype} {tuple(depth.shape)} on "
+                           f"{depth.device}")
+    depth = depth.detach().contiguous()
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    mip = int(mip or 0)
+    if images is not None:
+        if not 0 <= mip <= _lib.IMAGE_MIP_MAX:
+            raise RuntimeError(f"shacira_amd: mip must be in 0..{_lib.IMAGE_MIP_MAX}, got {mip}")
+        want = torch.uint16 if mip > 0 else torch.uint8
+        if (images.dtype != want or images.dim() != 4 or tuple(images.shape[:3]) != (V, H, W) or images.shape[3] not in (3, 4)
+                or images.device != dev):
+            raise RuntimeError(f"shacira_amd: expected {want} images [{V}, {H}, {W}, 3 or 4] on {dev}, got {images.dtype} "
+                               f"{tuple(images.shape)} on {images.device}")
+        images = images.contiguous()
+        if bg_color not in ("white", "black"):
+            raise RuntimeError(f"shacira_amd: bg_color must be 'white' or 'black', got {bg_color!r}")
+    return records, depth, images, (_ptr(records), V, W, H, _ptr(depth))
+
+
+def _image_tail(images, bg_color, mip):
+    return (_ptr(images), int(images.shape[3]), int(mip or 0),
+            _lib.RAYGEN_BG_BLACK if bg_color == "black" else _lib.RAYGEN_BG_WHITE)
+
+
+def depth_bounds(records, depth):
+    """(bounds, count) on the device, no read-back: fp32 [6] = the per-axis minimum then maximum of the points of all pixels of
+    ``depth`` (fp32 [V, H, W]) that are finite, and int64 [1], their number. +inf / -inf / 0 without one. Deterministic."""
+    records, depth, _, head = _depth_operands(records, depth)
+    dev = records.device
+    bounds = torch.empty((6,), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int64, device=dev)
+    if depth.numel() == 0:
+        bounds[:3], bounds[3:] = float("inf"), float("-inf")
+        count.zero_()
+        return bounds, count
+    with _on_device(dev):
+        _lib.check(_lib.lib().shacira_depth_bounds(*head, _ptr(bounds), _ptr(count), _stream(records)), "depth_bounds")
+    return bounds, count
+
+
+def depth_points(records, depth, images=None, bg_color="white", mip=0):
+    """(points fp32 [M, 3], colors uint8 [M, 3] or None): the points of the finite pixels of ``depth`` in (view, pixel) order and,
+    with ``images``, their composited colours as bytes. A counting launch, an exact int64 ``cumsum``, one read-back of M, a
+    writing launch (not capturable). Two calls return the same bits."""
+    records, depth, images, head = _depth_operands(records, depth, images, bg_color, mip)
+    dev = records.device
+    n = depth.numel()
+    blocks = (n + _lib.DEPTH_POINTS_BLOCK - 1) // _lib.DEPTH_POINTS_BLOCK
+    L = _lib.lib()
+    rows = 0
+    with _on_device(dev):
+        stream = _stream(records)
+        if blocks:
+            counts = torch.empty((blocks,), dtype=torch.int32, device=dev)
+            _lib.check(L.shacira_depth_points_count(*head, _ptr(counts), stream), "depth_points_count")
+            ends = torch.cumsum(counts, dim=0, dtype=torch.int64)          # integers: exact
+            rows = int(ends[-1].item())
+            offsets = ends - counts
+        points = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        colors = torch.empty((rows, 3), dtype=torch.uint8, device=dev) if images is not None else None
+        if rows > 0:
+            tail = _image_tail(images, bg_color, mip) if images is not None else (None, 3, 0, 0)
+            _lib.check(L.shacira_depth_points_emit(*head, *tail, _ptr(offsets), _ptr(points), _ptr(colors), stream),
+                       "depth_points_emit")
+    return points, colors
+
+
+def _spc_level(level):
+    level = int(level)
+    if not 1 <= level <= _lib.OCTREE_MAX_LEVEL:
+        raise RuntimeError(f"shacira_amd: an SPC level must be in 1..{_lib.OCTREE_MAX_LEVEL}, got {level}")
+    return level
+
+
+def spc_num_words(level):
+    return max(1, (1 << (3 * int(level))) // 32)
+
+
+def _spc_rank(words, level, stream):
+    """(rank int32, num_cells): the exclusive prefix of the words' popcounts and its total (one read-back: the colours' size)."""
+    pop = torch.empty_like(words)
+    _lib.check(_lib.lib().shacira_spc_rank(level, _ptr(words), _ptr(pop), stream), "spc_rank")
+    ends = torch.cumsum(pop, dim=0, dtype=torch.int32)                      # at most 2^30 cells: exact in int32
+    return ends - pop, int(ends[-1].item())
+
+
+def _spc_build(dev, level, mark, accumulate):
+    words = torch.zeros((spc_num_words(level),), dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        mark(words, stream)
+        rank, cells = _spc_rank(words, level, stream)
+        colors = None
+        if accumulate is not None:
+            colors = torch.empty((cells, 4), dtype=torch.uint8, device=dev)
+            if cells > 0:
+                sums = torch.zeros((cells, 4), dtype=torch.int64, device=dev)       # the kernel's uint64: the same bits
+                accumulate(words, rank, cells, sums, stream)
+                _lib.check(_lib.lib().shacira_spc_resolve(cells, _ptr(sums), _ptr(colors), stream), "spc_resolve")
+    return words, rank, colors, cells
+
+
+def spc_from_points(points, colors_u8, level):
+    """(words, rank, colors, num_cells) of the SPC of ``level`` holding ``points`` (fp32 [N, 3]; points that are not finite are
+    dropped, the others clamped into [-1, 1]^3's cells) with the rounded mean of ``colors_u8`` (uint8 [N, 3], or None: no
+    colours) per cell: mark, popcount + scan, accumulate, resolve -- no sort. Deterministic to the bit."""
+    _need_gpu(points, colors_u8)
+    level = _spc_level(level)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"shacira_amd: spc_from_points expects fp32 points [N, 3], got {points.dtype} {tuple(points.shape)}")
+    points = points.detach().contiguous()
+    N, dev = points.shape[0], points.device
+    if colors_u8 is not None:
+        if colors_u8.dtype != torch.uint8 or tuple(colors_u8.shape) != (N, 3) or colors_u8.device != dev:
+            raise RuntimeError(f"shacira_amd: spc_from_points expects uint8 colours [{N}, 3] on {dev}")
+        colors_u8 = colors_u8.contiguous()
+    L = _lib.lib()
+
+    def mark(words, stream):
+        _lib.check(L.shacira_spc_mark_points(N, _ptr(points), level, _ptr(words), stream), "spc_mark_points")
+
+    def accumulate(words, rank, cells, sums, stream):
+        _lib.check(L.shacira_spc_accumulate_points(N, _ptr(points), _ptr(colors_u8), level, _ptr(words), _ptr(rank), cells,
+                                                   _ptr(sums), stream), "spc_accumulate_points")
+    return _spc_build(dev, level, mark, accumulate if colors_u8 is not None else None)
+
+
+def spc_from_depth(records, depth, images, level, bg_color="white", mip=0):
+    """``spc_from_points`` of the cloud ``depth_points`` would make, without making it: the marking and the accumulating kernel
+    derive each point and colour from (view, pixel). The same bits as the two-step path."""
+    level = _spc_level(level)
+    records, depth, images, head = _depth_operands(records, depth, images, bg_color, mip)
+    L = _lib.lib()
+
+    def mark(words, stream):
+        _lib.check(L.shacira_spc_mark_depth(*head, level, _ptr(words), stream), "spc_mark_depth")
+
+    def accumulate(words, rank, cells, sums, stream):
+        _lib.check(L.shacira_spc_accumulate_depth(*head, *_image_tail(images, bg_color, mip), level, _ptr(words), _ptr(rank),
+                                                  cells, _ptr(sums), stream), "spc_accumulate_depth")
+    return _spc_build(records.device, level, mark, accumulate if images is not None else None)
+
+
+def spc_first_hit(origins, dirs, level, words, rank=None, colors=None):
+    """(depth fp32 [N], hit bool [N], pidx int32 [N], rgb fp32 [N, 3] or None) of the first occupied cell of ``level`` along every
+    ray, in ONE launch: the first nugget of ``render.raytrace_dense`` on the same set (same ``pidx``, entry depth bit for bit).
+    A miss -- and any ray with a component that is not finite -- gives 0 / False / -1 / 0. ``words``: the packed occupancy;
+    ``rank`` and ``colors`` (uint8 [cells, 4]) give ``rgb`` = byte / 255, None without them."""
+    _need_gpu(origins, dirs, words, rank, colors)
+    level = _spc_level(level)
+    dev = origins.device
+    origins = _rows(origins.detach().contiguous(), "origins", dev=dev)
+    dirs = _rows(dirs.detach().contiguous(), "dirs", dev=dev, n=origins.shape[0])
+    N = origins.shape[0]
+    want_rgb = colors is not None
+    words = _u32_operand(words, (spc_num_words(level),), dev, "words", "spc_first_hit")
+    if (rank is None) != (colors is None):
+        raise RuntimeError("shacira_amd: spc_first_hit takes rank and colors together, or neither")
+    if colors is not None:
+        rank = _u32_operand(rank, (spc_num_words(level),), dev, "rank", "spc_first_hit")
+        if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[1] != 4 or colors.device != dev:
+            raise RuntimeError(f"shacira_amd: spc_first_hit expects uint8 colors [cells, 4] on {dev}")
+        colors = colors.contiguous()
+        if colors.shape[0] == 0:            # an empty SPC: nothing can be hit, nothing is looked up
+            rank = colors = None
+    depth = torch.empty((N,), dtype=torch.float32, device=dev)
+    hit = torch.empty((N,), dtype=torch.bool, device=dev)
+    pidx = torch.empty((N,), dtype=torch.int32, device=dev)
+    rgb = torch.zeros((N, 3), dtype=torch.float32, device=dev) if want_rgb else None
+    if N > 0:
+        with _on_device(dev):
+            rc = _lib.lib().shacira_spc_first_hit(N, _ptr(origins), _ptr(dirs), level, _ptr(words), _ptr(rank), _ptr(colors),
+                                                  _ptr(depth), _ptr(hit), _ptr(pidx), _ptr(rgb), _stream(origins))
+        _lib.check(rc, "spc_first_hit")
+    return depth, hit, pidx, rgb
 
 
 # ---- pixel batches and the pixel loss (include/shacira_hip.h, shacira_pixel_batch / shacira_pixel_loss_*) -----------------------

@@ -198,6 +198,26 @@ class OctreeAS(BaseAS):
                                                   level)
         return ASRaytraceResults(ridx=ridx, pidx=pidx, depth=depth if with_exit else depth[:, 0:1])
 
+    def first_hit(self, rays, level=None):
+        """(hit bool [N], pidx int32 [N], depth fp32 [N]): the first occupied cell of ``level`` along every ray -- the first
+        nugget of ``raytrace`` per ray (same ``pidx``, entry depth bit for bit) -- in ONE launch that writes one row per ray
+        (spc.hip, shacira_spc_first_hit) instead of every crossing. A miss gives False / -1 / 0. The kernel reads the packed
+        words: the structure's own for ``max_level`` (packed once from the bool grid and kept when it has none)."""
+        from ... import hip_ops
+        from ..ops.spc.structured import pack_occupancy
+        level = self._level(level)
+        if level < 1:
+            raise ValueError("first_hit needs a level >= 1")
+        dev = rays.origins.device
+        grid = self.occupancy_at(level, dev)
+        words = self.packed_occupancy(level)
+        if words is None or words.device != dev:
+            words = pack_occupancy(grid)
+            if level == self.max_level:
+                self._packed = (self.occupancy_grid, words)
+        depth, hit, pidx, _ = hip_ops.spc_first_hit(rays.origins, rays.dirs, level, words)
+        return hit, pidx, depth
+
     def _raymarch_voxel(self, rays, num_samples, level=None) -> ASRaymarchResults:
         """num_samples jittered samples inside every intersected cell (reference octree_as.py:171-233)."""
         from ... import render

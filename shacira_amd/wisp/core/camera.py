@@ -192,6 +192,32 @@ class Camera:
         rot_t = self._view[:, :3, :3].transpose(1, 2)
         return -(rot_t @ self._view[:, :3, 3:4]).squeeze(-1)
 
+    @property
+    def t(self):
+        """[V, 3, 1]: the translation column of the view matrices (kaolin's ``extrinsics.t``)."""
+        return self._view[:, :3, 3:4]
+
+    @t.setter
+    def t(self, value):
+        """In place: the translation column replaced, the rotation kept. With ``value = s * t`` the camera position -R^T t is
+        scaled by s about the world's origin."""
+        self._view[:, :3, 3] = torch.as_tensor(value, dtype=self.dtype, device=self.device).reshape(-1, 3)
+
+    def translate(self, offset):
+        """In place: the cameras moved by ``offset`` [3] (or [V, 3]) in the world, rotation unchanged -- ``cam_pos()`` becomes
+        ``cam_pos() + offset`` (kaolin's ``extrinsics.translate``: t becomes t - R offset)."""
+        offset = torch.as_tensor(offset, dtype=self.dtype, device=self.device).reshape(-1, 3)
+        self._view[:, :3, 3] = self._view[:, :3, 3] - (self._view[:, :3, :3] @ offset.expand(len(self), 3).unsqueeze(-1)).squeeze(-1)
+        return self
+
+    def normalize(self, center, scale):
+        """In place, the net effect of ``translate(-center)`` followed by ``t = t * scale``: the camera position becomes
+        (pos - center) * scale, the rotation is unchanged -- what a data set applies to its ray origins when it moves and
+        scales its point cloud into [-1, 1]^3."""
+        self.translate(-torch.as_tensor(center, dtype=self.dtype, device=self.device))
+        self.t = self.t * float(scale)
+        return self
+
     def change_coordinate_system(self, basis_change):
         """In place: the world's points p become B p (B a 3x3 orthonormal basis change). The view matrix becomes V B4^-1, so
         every camera-space point, and with it the picture, stays what it was."""
