@@ -24,8 +24,8 @@ constexpr int kSymLdsBins = 12288;   // 48 KiB of private uint32 bins per workgr
 __device__ __forceinline__ int32_t to_symbol(float v) {
     // torch.round (half to even) then .long(); clamped so that lo/hi arithmetic cannot overflow. NaN -> 0.
     const float r = rintf(v);
-    const float c = fminf(fmaxf(r, -1073741824.0f), 1073741824.0f);
-    return (c == c) ? (int32_t)c : 0;
+    const float c = fminf(fmaxf(r, -1073741824.0f), 1073741824.0f);   // fmaxf / fminf drop a NaN operand: test r, not c
+    return (r == r) ? (int32_t)c : 0;
 }
 
 __global__ void symbol_range_init_kernel(int32_t *__restrict__ minmax, int ld) {

@@ -1,6 +1,7 @@
 """numpy reference of the "rans64" channel format (include/shacira_hip.h, "Interleaved rANS"): 64 coder states per block
 advance in lockstep and share one stream of 16-bit words. Vectorised over lanes and blocks, loops over the step k. This is
-the oracle of tests/test_rans_cpu.py and tests/test_gpu_rans.py; it shares no code with the library."""
+the oracle of tests/test_rans_cpu.py, tests/test_gpu_rans.py and tests/test_gpu_rans_edges.py; it shares no code with the
+library. The edge models, corruptions and limit latents those files share are built below the coder."""
 import numpy as np
 
 LANES = 64
@@ -97,6 +98,132 @@ def split_payload(payload, T, K):
 def decode_payload(payload, freq, T, K):
     n_b, states, words = split_payload(payload, T, K)
     return decode_blocks(n_b, states, words, freq, T, K)
+
+
+def block_starts(n_b):
+    """exclusive prefix of the per-block word counts: the index of a block's first word in the channel's stream"""
+    n_b = np.asarray(n_b, dtype=np.int64)
+    return np.cumsum(n_b) - n_b
+
+
+# ---- one-step corruptions of a well-formed payload (the sections keep their sizes; the count sum is preserved) ----
+def flip_word(payload, T, K, index, bit):
+    nblocks = -(-T // (LANES * K))
+    out = bytearray(payload)
+    out[260 * nblocks + 2 * index + bit // 8] ^= 1 << (bit % 8)
+    return bytes(out)
+
+
+def flip_state(payload, T, K, block, lane, bit):
+    nblocks = -(-T // (LANES * K))
+    out = bytearray(payload)
+    out[4 * nblocks + 4 * (block * LANES + lane) + bit // 8] ^= 1 << (bit % 8)
+    return bytes(out)
+
+
+def swap_counts(payload, T, K, b0, b1):
+    out = bytearray(payload)
+    out[4 * b0:4 * b0 + 4], out[4 * b1:4 * b1 + 4] = payload[4 * b1:4 * b1 + 4], payload[4 * b0:4 * b0 + 4]
+    return bytes(out)
+
+
+# ---- hand-built models at the coder's edges: name -> (symbols int64 [T, ld], [freq per channel], lo per channel, K) ----
+T_EDGE = 64 * 4 * 3 + 5            # K = 4: three full blocks and one of five symbols
+
+
+def _sparse(T, at, common, rare):
+    sym = np.full(T, common, dtype=np.int64)
+    sym[list(at)] = rare
+    return sym[:, None]
+
+
+def _u32(*f):
+    return np.array(f, dtype=np.uint32)
+
+
+def gauss_case(normalise, T=64 * 16 * 2 + 37, ld=2, sigma=6.0, seed=24):
+    """~40 bins per channel under `normalise` (counts -> frequencies that sum to 2^16) of each channel's own counts, so
+    bin 0 and the last bin are present as in a container; K = 16: two full blocks and one of 37 symbols that emits nothing."""
+    rng = np.random.default_rng(seed)
+    sym = np.rint(rng.standard_normal((T, ld)) * sigma).astype(np.int64)
+    lo = sym.min(axis=0)
+    sym = sym - lo[None, :]
+    freqs = [normalise(np.bincount(sym[:, c])) for c in range(ld)]
+    return sym, freqs, [int(v) for v in lo], 16
+
+
+def model_edge_cases(normalise):
+    rng = np.random.default_rng(17)
+    T, at = T_EDGE, (10, 64 * 4 * 3 + 2)                             # outliers in the first and the last block only
+    cases = {
+        "dominant_first": (_sparse(T, at, 0, 1), [_u32(65535, 1)], [7], 4),
+        "dominant_first_plateau": (_sparse(T, at, 0, 3), [_u32(65535, 0, 0, 1)], [-5], 4),
+        "dominant_last": (_sparse(T, at, 1, 0), [_u32(1, 65535)], [0], 4),
+        "flat_65536": (rng.integers(0, 65536, (64 * 4 * 2 + 37, 1)), [np.ones(65536, np.uint32)], [-32768], 4),
+    }
+    f4095 = np.full(4095, 16, dtype=np.uint32)
+    f4095[:16] += 1                                                  # 4095 * 16 + 16 = 65536
+    f4096 = np.concatenate([f4095, [1]]).astype(np.uint32)           # the extra bin at f = 1 ...
+    f4096[0] -= 1                                                    # ... taken from bin 0
+    below = rng.integers(0, 4095, (T, 1))
+    below[:3, 0] = (0, 4094, 15)
+    cases["lds_4095"] = (below, [f4095], [3], 4)
+    cases["lds_4096"] = (below, [f4096], [3], 4)
+    cases["lds_4095_beside_4096"] = (np.concatenate([below, below[::-1]], axis=1), [f4095, f4096], [-4000, 100], 4)
+    cases["gauss"] = gauss_case(normalise)
+    return cases
+
+
+def sparse_outliers(T, rate, seed):
+    """symbols of a (65535, 1) model: 0 except for 1s at `rate`; the last symbol is a 0"""
+    sym = (np.random.default_rng(seed).random(T) < rate).astype(np.int64)
+    sym[-1] = 0
+    return sym
+
+
+def container_limit_latents():
+    """name -> fp32 [T, ld] latents whose containers sit on the format's limits (the values carry fractions that round away)"""
+    rng = np.random.default_rng(23)
+    cases = {"permutation_65536": (rng.permutation(65536) - 30000).astype(np.float32)[:, None]}   # every f = 1
+    spike = np.zeros((70_000, 1), dtype=np.float32)
+    spike[41_234] = 3.0                                              # counts (69999, 0, 0, 1) -> freq (65535, 0, 0, 1)
+    cases["spike_in_zeros"] = spike
+    T = 4301
+    dominant = np.zeros(T)
+    dominant[[5, 2000, T - 1]] = 3.0
+    kinds = [np.full(T, -3.0), rng.integers(0, 2, T).astype(np.float64), dominant, np.rint(rng.standard_normal(T) * 2.0),
+             rng.permutation(T) % 4095, rng.permutation(T) % 4096]
+    cols = [kinds[c % 6] + (0, 11, -700, 2500)[c % 4] * (c // 6) for c in range(16)]
+    mix = np.stack(cols, axis=1) + rng.uniform(-0.3, 0.3, (T, 16))
+    cases["sixteen_kinds"] = mix.astype(np.float32)
+    return cases
+
+
+def payload_corruptions(payload, T, K):
+    """[(name, corrupt payload)]: single flipped bits in words and final states, and swapped block counts. Deterministic."""
+    n_b, states, words = split_payload(payload, T, K)
+    nblocks = n_b.size
+    starts = block_starts(n_b)
+    rng = np.random.default_rng(5)
+    out = []
+    picks = {0: 0, int(words.size) - 1: 15}                          # word index -> bit
+    for b in range(nblocks):
+        if n_b[b]:
+            picks.setdefault(int(starts[b]), 7)                      # first and last word of every block that has any
+            picks.setdefault(int(starts[b] + n_b[b]) - 1, 8)
+    for w in rng.integers(0, words.size, 10):
+        picks.setdefault(int(w), int(rng.integers(0, 16)))
+    out += [(f"word{w}^bit{bit}", flip_word(payload, T, K, w, bit)) for w, bit in sorted(picks.items())]
+    for b in range(nblocks):
+        live = min(LANES, T - b * LANES * K)                         # lanes of the block that own a symbol
+        lanes = {0: 0, live - 1: 31, live // 2: 16}
+        if live < LANES:
+            lanes.update({live: 0, LANES - 1: 16})                   # idle lanes hold 2^16: bit 16 pushes them to 0
+        out += [(f"state{b}.{l}^bit{bit}", flip_state(payload, T, K, b, l, bit)) for l, bit in sorted(lanes.items())]
+    low = np.argwhere(states < (1 << 17))                            # bit 16 of these pushes the state below 2^16
+    out += [(f"state{b}.{l}->below", flip_state(payload, T, K, int(b), int(l), 16)) for b, l in low[:4]]
+    out += [(f"counts{b}<->{b + 1}", swap_counts(payload, T, K, b, b + 1)) for b in range(nblocks - 1)]
+    return out
 
 
 def model_bytes(sym, freq):

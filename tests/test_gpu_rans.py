@@ -1,6 +1,7 @@
 """The "rans64" kernels of symbols.hip on the MI355X: device containers equal host containers byte for byte, and the device
 decoder restores round(latent) bit for bit -- from containers written by either side. The host coder is held to the numpy
-reference by tests/test_rans_cpu.py. Only well-formed payloads reach the device decoder here."""
+reference by tests/test_rans_cpu.py. Only well-formed payloads reach the device decoder here; corrupt ones, hand-built models
+and the format's limits are in tests/test_gpu_rans_edges.py."""
 import struct
 
 import numpy as np

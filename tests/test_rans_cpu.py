@@ -104,6 +104,83 @@ def test_fuzz_over_length_steps_and_bins():
         _check_case(sym, freq, K)
 
 
+# ---- the host-coder twins of tests/test_gpu_rans_edges.py: the same inputs, held to the reference without a GPU ----
+EDGE_CASES = R.model_edge_cases(codec.normalise_frequencies)
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_CASES))
+def test_model_edges(name):
+    sym, freqs, lo, K = EDGE_CASES[name]
+    T = sym.shape[0]
+    for c, freq in enumerate(freqs):
+        n_b, _, words = R.split_payload(_check_case(sym[:, c], freq, K), T, K)
+        if name.startswith("dominant"):
+            assert n_b.tolist() == [1, 0, 0, 1]                      # only the outliers emit: the middle blocks are empty
+        if name == "flat_65536":
+            assert n_b.tolist() == [256, 256, 37] and words.size == T    # one word per symbol: the slot bound is met
+        if name == "gauss":
+            assert n_b[:2].min() > 0 and n_b[2] == 0 and 35 <= freq.size <= 60
+
+
+@pytest.mark.parametrize("T", [1, 63, 64, 65, 128, 129])
+def test_one_step_per_block(T):
+    sym = R.known_answer_symbols(T)
+    n_b, _, _ = R.split_payload(_check_case(sym, R.KNOWN_FREQ, 1), T, 1)
+    assert n_b.size == -(-T // 64) and not n_b.any()                 # a state's first symbol never emits (every f > 1)
+    _check_case(R.sparse_outliers(T, 0.1, T) ^ 1, np.array([1, 65535], dtype=np.uint32), 1)
+
+
+def test_payload_corruptions_host_verdict_is_the_references():
+    sym, freqs, lo, K = EDGE_CASES["gauss"]
+    T, c = sym.shape[0], 1
+    good = R.encode_payload(sym[:, c], freqs[c], K)
+    lat = torch.from_numpy((sym + np.asarray(lo)[None, :]).astype(np.float32))
+    blob = codec.compress_latents(lat, coder="rans", steps=K)
+    off = codec._parse_rans(blob)[3][c]["payload_off"]
+    assert blob[off:off + len(good)] == good
+    cases = R.payload_corruptions(good, T, K)
+    names = " ".join(n for n, _ in cases)
+    assert len(cases) >= 25 and "word" in names and "below" in names and "state2." in names and "counts1<->2" in names
+    for name, bad in cases:
+        assert len(bad) == len(good) and bad != good, name
+        want, ok = R.decode_payload(bad, freqs[c], T, K)
+        container = blob[:off] + bad + blob[off + len(bad):]
+        if ok:
+            assert np.array_equal(codec.rans_decode(bad, freqs[c], T, K), want), name
+            assert torch.equal(codec.decompress_latents(container)[:, c], torch.from_numpy(want + lo[c]).float()), name
+        else:
+            with pytest.raises(ValueError):
+                codec.rans_decode(bad, freqs[c], T, K)
+            with pytest.raises(ValueError):
+                codec.decompress_latents(container)
+
+
+LIMIT_LATENTS = R.container_limit_latents()
+
+
+@pytest.mark.parametrize("name", sorted(LIMIT_LATENTS))
+def test_containers_at_the_limits(name):
+    lat = torch.from_numpy(LIMIT_LATENTS[name])
+    blob = codec.compress_latents(lat, coder="rans", steps=4)
+    T, ld, K, chans = codec._parse_rans(blob)
+    sym = np.rint(LIMIT_LATENTS[name]).astype(np.int64)
+    for c, ch in enumerate(chans):
+        if ch["nbins"] > 1:
+            size = 260 * -(-T // (64 * K)) + 2 * ch["words"]
+            assert blob[ch["payload_off"]:ch["payload_off"] + size] == R.encode_payload(sym[:, c] - ch["lo"], ch["freq"], K)
+    assert torch.equal(codec.decompress_latents(blob), torch.round(lat))
+    if name == "permutation_65536":
+        assert chans[0]["nbins"] == codec.RC_TOTAL and chans[0]["words"] == T and (chans[0]["freq"] == 1).all()
+        wider = torch.arange(-7, 65530, dtype=torch.float32)[torch.randperm(65537, generator=torch.Generator().manual_seed(1))]
+        with pytest.raises(ValueError):
+            codec.compress_latents(wider[:, None], coder="rans", steps=4)         # 65 537 consecutive integers
+    if name == "spike_in_zeros":
+        assert chans[0]["freq"].tolist() == [65535, 0, 0, 1] and chans[0]["words"] == 1
+        assert chans[0]["n_b"].size == 274 and int((chans[0]["n_b"] == 0).sum()) == 273
+    if name == "sixteen_kinds":
+        assert [ch["nbins"] for ch in chans[:6]] == [1, 2, 4, chans[3]["nbins"], 4095, 4096] and 8 < chans[3]["nbins"] < 30
+
+
 SHAPES = [(5000, 1), (4096, 2), (777, 3), (0, 2), (1, 16)]
 
 
