@@ -1,6 +1,7 @@
 """numpy restatement of the shacira_mesh_voxelize contract (include/shacira_hip.h): the same fp32 operation sequence, one
-rounding per operator, so the cell set is reproduced EXACTLY. Also the meshes and an fp64 separating-axis test the tests share.
-Written from the contract alone."""
+rounding per operator, so the cell set is reproduced EXACTLY: dense (``mesh_voxelize_ref``) and, by the same formulas, as
+sorted keys (``mesh_voxelize_keys``) for the levels whose G^3 cells do not fit. Also the meshes and an fp64 separating-axis
+test the tests share. Written from the contract alone."""
 import numpy as np
 
 from mesh_sdf_ref import cube, icosphere  # noqa: F401  (the shared meshes)
@@ -12,11 +13,11 @@ def _cross(x, y):
     return (x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0])
 
 
-def mesh_voxelize_ref(triangles, level, margin):
-    """bool [G, G, G], indexed [x][y][z]: the cells the contract sets."""
+def _boxes(triangles, level, margin):
+    """Per valid triangle with a non-empty clipped bounding box: (lo int64 [3], hi int64 [3], bool [hi - lo + 1]: the cells of
+    the box that the contract sets), in the order of the triangles."""
     tri = np.ascontiguousarray(triangles, dtype=F32).reshape(-1, 3, 3)
     G = 1 << level
-    grid = np.zeros((G, G, G), dtype=bool)
     half = F32(0.5) * F32(G)
     H = F32(0.5) + F32(margin)
     with np.errstate(all="ignore"):
@@ -48,8 +49,57 @@ def mesh_voxelize_ref(triangles, level, margin):
                     r = H * (abs(mu) + abs(mv))
                     f = (mu * (p[u] - P[i, u]) + mv * (p[v] - P[i, v])) + r
                     ok = ok & (f >= 0)
-            grid[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] |= ok
+            yield lo, hi, ok
+
+
+def mesh_voxelize_ref(triangles, level, margin):
+    """bool [G, G, G], indexed [x][y][z]: the cells the contract sets."""
+    G = 1 << level
+    grid = np.zeros((G, G, G), dtype=bool)
+    for lo, hi, ok in _boxes(triangles, level, margin):
+        grid[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] |= ok
     return grid
+
+
+def mesh_voxelize_keys(triangles, level, margin):
+    """int64, sorted and unique: the keys (x * G + y) * G + z of the cells the contract sets -- ``mesh_voxelize_ref`` by the
+    same formulas without the G^3 cells, so that the deepest levels have a reference."""
+    G = 1 << level
+    keys = [np.zeros(0, dtype=np.int64)]
+    for lo, hi, ok in _boxes(triangles, level, margin):
+        x, y, z = np.nonzero(ok)
+        keys.append(((x + lo[0]) * G + (y + lo[1])) * G + (z + lo[2]))
+    return np.unique(np.concatenate(keys))
+
+
+def words_of_keys(keys):
+    """(word index int64 [W] ascending, uint32 [W]): the non-zero words of ``pack_words`` from sorted unique keys."""
+    word, inverse = np.unique(keys >> 5, return_inverse=True)
+    bits = np.zeros(word.shape[0], dtype=np.uint32)
+    np.bitwise_or.at(bits, inverse, np.uint32(1) << (keys & 31).astype(np.uint32))
+    return word, bits
+
+
+def unit_counts(triangles, level, margin):
+    """int64 [T]: the column words of every triangle -- the (x, y) columns of its clipped bounding box times the 32-bit words
+    its z range touches -- 0 for an invalid triangle or an empty box. The box does not depend on the overlap test."""
+    tri = np.ascontiguousarray(triangles, dtype=F32).reshape(-1, 3, 3)
+    G = 1 << level
+    half = F32(0.5) * F32(G)
+    H = F32(0.5) + F32(margin)
+    out = np.zeros(tri.shape[0], dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for j, t in enumerate(tri):
+            n = _cross(t[1] - t[0], t[0] - t[2])
+            P = (t + F32(1.0)) * half
+            if not (n[0] != 0 or n[1] != 0 or n[2] != 0) or not np.isfinite(P).all():
+                continue
+            lo = np.maximum(np.ceil((P.min(axis=0) - H) - F32(0.5)), F32(0.0))
+            hi = np.minimum(np.floor((P.max(axis=0) + H) - F32(0.5)), F32(G - 1))
+            if (lo <= hi).all():
+                lo, hi = lo.astype(np.int64), hi.astype(np.int64)
+                out[j] = (hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * ((hi[2] >> 5) - (lo[2] >> 5) + 1)
+    return out
 
 
 def pack_words(grid):
