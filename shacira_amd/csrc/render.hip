@@ -8,6 +8,7 @@
 //
 // A pack = the consecutive samples of one ray, [pack_start[r], pack_start[r+1]). One 64-lane wave walks one pack in
 // chunks of 64 samples: loads are coalesced, the running optical depth is a wave scan plus a carry.
+#include "grid_walk.h"
 #include "internal.h"
 
 namespace shacira {
@@ -240,16 +241,9 @@ __global__ __launch_bounds__(64 * kPackWaves) void raymarch_ray_kernel(
         if (lane == 0) counts[r] = total;
 }
 
-// Ray / occupied-cell intersections on the dense grid, ordered by depth (3-D DDA, Amanatides & Woo); thread per ray.
+// Ray / occupied-cell intersections on the dense grid, ordered by depth (the walk of grid_walk.h); thread per ray.
 // EMIT = false: counts[r]; EMIT = true: ridx / pidx (Morton index of the cell, x most significant) / depth [K, 2]
 // (entry clipped to 0 for rays starting inside the volume).
-__device__ __forceinline__ uint32_t morton_x_major(uint32_t x, uint32_t y, uint32_t z, int level) {
-    uint32_t m = 0;
-    for (int b = 0; b < level; ++b)
-        m |= (((x >> b) & 1u) << (3 * b + 2)) | (((y >> b) & 1u) << (3 * b + 1)) | (((z >> b) & 1u) << (3 * b));
-    return m;
-}
-
 template <bool EMIT>
 __global__ __launch_bounds__(256) void raytrace_dense_kernel(int64_t num_rays, const float *__restrict__ origins,
                                                              const float *__restrict__ dirs,
@@ -261,70 +255,21 @@ __global__ __launch_bounds__(256) void raytrace_dense_kernel(int64_t num_rays, c
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= num_rays) return;
     const int G = 1 << level;
-    const float o[3] = {origins[r * 3], origins[r * 3 + 1], origins[r * 3 + 2]};
-    const float d[3] = {dirs[r * 3], dirs[r * 3 + 1], dirs[r * 3 + 2]};
-    // slab test against [-1, 1]^3
-    float tn = -INFINITY, tf = INFINITY;
-    bool miss = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (d[a] == 0.0f) {
-            if (o[a] < -1.0f || o[a] > 1.0f) miss = true;
-        } else {
-            const float inv = 1.0f / d[a];
-            const float t0 = (-1.0f - o[a]) * inv, t1 = (1.0f - o[a]) * inv;
-            tn = fmaxf(tn, fminf(t0, t1));
-            tf = fminf(tf, fmaxf(t0, t1));
-        }
-    }
     int32_t n = 0;
     int64_t out = EMIT ? offsets[r] : 0;
-    if (!miss && tf > fmaxf(tn, 0.0f)) {
-        float t = fmaxf(tn, 0.0f);
-        const float cell = 2.0f / (float)G;
-        int c[3], step[3];
-        float tmax[3], tdelta[3];
-        const float tin = t;   // a start cell that is off by one rounding is skipped by the walk (zero-length stay)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float p = fmaf(d[a], tin, o[a]);
-            int q = (int)floorf((p + 1.0f) * 0.5f * (float)G);
-            q = q < 0 ? 0 : (q > G - 1 ? G - 1 : q);
-            c[a] = q;
-            if (d[a] > 0.0f) {
-                step[a] = 1;
-                tdelta[a] = cell / d[a];
-                tmax[a] = ((-1.0f + (float)(q + 1) * cell) - o[a]) / d[a];
-            } else if (d[a] < 0.0f) {
-                step[a] = -1;
-                tdelta[a] = -cell / d[a];
-                tmax[a] = ((-1.0f + (float)q * cell) - o[a]) / d[a];
-            } else {
-                step[a] = 0;
-                tdelta[a] = INFINITY;
-                tmax[a] = INFINITY;
-            }
-        }
-        for (int it = 0; it < 3 * G + 3; ++it) {
-            const int a = (tmax[0] <= tmax[1]) ? ((tmax[0] <= tmax[2]) ? 0 : 2) : ((tmax[1] <= tmax[2]) ? 1 : 2);
-            const float texit = fminf(tmax[a], tf);
-            if (texit > t && occupied(occ, G, c[0], c[1], c[2])) {
-                if constexpr (EMIT) {
-                    ridx[out] = (int32_t)r;
-                    pidx[out] = (int32_t)morton_x_major((uint32_t)c[0], (uint32_t)c[1], (uint32_t)c[2], level);
-                    depth[out * 2] = t;
-                    depth[out * 2 + 1] = texit;
-                    ++out;
-                }
-                ++n;
-            }
-            t = fmaxf(t, texit);
-            if (tmax[a] >= tf) break;
-            c[a] += step[a];
-            if (c[a] < 0 || c[a] >= G) break;
-            tmax[a] += tdelta[a];
-        }
-    }
+    grid_walk(origins[r * 3], origins[r * 3 + 1], origins[r * 3 + 2], dirs[r * 3], dirs[r * 3 + 1], dirs[r * 3 + 2], level,
+              [&](int cx, int cy, int cz, float t, float texit) {
+                  if (!occupied(occ, G, cx, cy, cz)) return false;
+                  if constexpr (EMIT) {
+                      ridx[out] = (int32_t)r;
+                      pidx[out] = (int32_t)morton_x_major((uint32_t)cx, (uint32_t)cy, (uint32_t)cz, level);
+                      depth[out * 2] = t;
+                      depth[out * 2 + 1] = texit;
+                      ++out;
+                  }
+                  ++n;
+                  return false;
+              });
     if constexpr (!EMIT) counts[r] = n;
 }
 

@@ -11,15 +11,14 @@
 //                        64-bit integer atomics (exact, so order-independent). Both are ONE template over the source of the
 //                        points: an fp32 cloud, or (camera records, depth plane, images) -- the cloud is then never materialised.
 //   spc_popcount, spc_resolve    the popcount per word (the caller scans it into `rank`) and the rounded integer mean per slot.
-//   spc_first_hit        one lane per ray: raytrace_dense's walk (render.hip) -- the same slab test, the same tmax += tdelta
-//                        accumulation, the same tie order of the axes -- that stops at the first occupied cell and reads bits of
-//                        the packed words instead of bytes. Written with select chains, not indexed arrays: no private segment.
+//   spc_first_hit        one lane per ray: the walk of grid_walk.h (shared with render.hip) stopped at the first set bit of `words`.
 // The point of a pixel is o + d * depth with raygen's origin and unit direction (raygen_device.h), two roundings per axis; the
 // library is built with -ffp-contract=off, so no product is fused into the sum. All address arithmetic is 64-bit.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "grid_walk.h"
 #include "internal.h"
 #include "raygen_device.h"
 
@@ -282,47 +281,6 @@ __global__ void __launch_bounds__(kSpcBlock) spc_resolve_kernel(int64_t cells, c
 }
 
 // ---- first hit ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t morton_x_major(uint32_t x, uint32_t y, uint32_t z, int level) {
-    uint32_t m = 0;
-    for (int b = 0; b < level; ++b)
-        m |= (((x >> b) & 1u) << (3 * b + 2)) | (((y >> b) & 1u) << (3 * b + 1)) | (((z >> b) & 1u) << (3 * b));
-    return m;
-}
-
-// one axis of the slab test against [-1, 1] (render.hip, raytrace_dense_kernel)
-__device__ __forceinline__ void slab_axis(float o, float d, float &tn, float &tf, bool &miss) {
-    if (d == 0.0f) {
-        if (o < -1.0f || o > 1.0f) miss = true;
-    } else {
-        const float inv = 1.0f / d;
-        const float t0 = (-1.0f - o) * inv, t1 = (1.0f - o) * inv;
-        tn = fmaxf(tn, fminf(t0, t1));
-        tf = fminf(tf, fmaxf(t0, t1));
-    }
-}
-
-// one axis of the walk's set-up: the start cell, the step, the depth of the next crossing and the depth between crossings
-__device__ __forceinline__ void walk_axis(float o, float d, float tin, int G, float cell, int &c, int &step, float &tmax,
-                                          float &tdelta) {
-    const float p = fmaf(d, tin, o);
-    int q = (int)floorf((p + 1.0f) * 0.5f * (float)G);
-    q = q < 0 ? 0 : (q > G - 1 ? G - 1 : q);
-    c = q;
-    if (d > 0.0f) {
-        step = 1;
-        tdelta = cell / d;
-        tmax = ((-1.0f + (float)(q + 1) * cell) - o) / d;
-    } else if (d < 0.0f) {
-        step = -1;
-        tdelta = -cell / d;
-        tmax = ((-1.0f + (float)q * cell) - o) / d;
-    } else {
-        step = 0;
-        tdelta = INFINITY;
-        tmax = INFINITY;
-    }
-}
-
 __global__ void __launch_bounds__(kSpcBlock) spc_first_hit_kernel(int64_t num_rays, const Float3 *__restrict__ origins,
                                                                   const Float3 *__restrict__ dirs, int level,
                                                                   const uint32_t *__restrict__ words,
@@ -340,53 +298,16 @@ __global__ void __launch_bounds__(kSpcBlock) spc_first_hit_kernel(int64_t num_ra
     bool found = false;
     const bool finite = finite_bits(o.x) && finite_bits(o.y) && finite_bits(o.z) && finite_bits(d.x) && finite_bits(d.y) &&
                         finite_bits(d.z);
-    if (finite) {
-        float tn = -INFINITY, tf = INFINITY;
-        bool miss = false;
-        slab_axis(o.x, d.x, tn, tf, miss);
-        slab_axis(o.y, d.y, tn, tf, miss);
-        slab_axis(o.z, d.z, tn, tf, miss);
-        if (!miss && tf > fmaxf(tn, 0.0f)) {
-            float t = fmaxf(tn, 0.0f);
-            const float cell = 2.0f / (float)G;
-            const float tin = t;
-            int cx, cy, cz, sx, sy, sz;
-            float mx, my, mz, ex, ey, ez;             // tmax and tdelta per axis
-            walk_axis(o.x, d.x, tin, G, cell, cx, sx, mx, ex);
-            walk_axis(o.y, d.y, tin, G, cell, cy, sy, my, ey);
-            walk_axis(o.z, d.z, tin, G, cell, cz, sz, mz, ez);
-            for (int it = 0; it < 3 * G + 3; ++it) {
-                const int a = (mx <= my) ? ((mx <= mz) ? 0 : 2) : ((my <= mz) ? 1 : 2);
-                const float tm = a == 0 ? mx : (a == 1 ? my : mz);
-                const float texit = fminf(tm, tf);
-                if (texit > t) {
-                    const uint32_t key = ((uint32_t)cx * (uint32_t)G + (uint32_t)cy) * (uint32_t)G + (uint32_t)cz;
-                    if ((words[key >> 5] >> (key & 31u)) & 1u) {
-                        found = true;
-                        out_depth = t;
-                        out_key = key;
-                        out_pidx = (int32_t)morton_x_major((uint32_t)cx, (uint32_t)cy, (uint32_t)cz, level);
-                        break;
-                    }
-                }
-                t = fmaxf(t, texit);
-                if (tm >= tf) break;
-                if (a == 0) {
-                    cx += sx;
-                    if (cx < 0 || cx >= G) break;
-                    mx += ex;
-                } else if (a == 1) {
-                    cy += sy;
-                    if (cy < 0 || cy >= G) break;
-                    my += ey;
-                } else {
-                    cz += sz;
-                    if (cz < 0 || cz >= G) break;
-                    mz += ez;
-                }
-            }
-        }
-    }
+    if (finite)                                       // a ray that is not finite is a miss by contract
+        grid_walk(o.x, o.y, o.z, d.x, d.y, d.z, level, [&](int cx, int cy, int cz, float t, float) {
+            const uint32_t key = ((uint32_t)cx * (uint32_t)G + (uint32_t)cy) * (uint32_t)G + (uint32_t)cz;
+            if (!((words[key >> 5] >> (key & 31u)) & 1u)) return false;
+            found = true;
+            out_depth = t;
+            out_key = key;
+            out_pidx = (int32_t)morton_x_major((uint32_t)cx, (uint32_t)cy, (uint32_t)cz, level);
+            return true;
+        });
     depth[r] = out_depth;
     hit[r] = found ? 1 : 0;
     pidx[r] = out_pidx;

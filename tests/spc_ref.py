@@ -10,11 +10,12 @@ Cells, slots, colours. Integers: the cell of an fp32 point is the fp32 expressio
 numpy float32 operators (one rounding each, as the kernel's); keys, words, ranks, slots, colour sums and the rounded means
 (2 sum + n) // (2 n) are int64 and exact.
 
-First hit. "The first nugget of a flat fp32 DDA": the slab test and the Amanatides-Woo walk of shacira_raytrace_dense in numpy
-float32 scalars, stopping at the first occupied cell whose stay has positive length. The one fused operation of the walk's
-set-up, fmaf(d, tin, o), is evaluated in fp64 and rounded to fp32 (the product is exact in fp64; the sum rounds twice, which can
-differ from the fused result only when the fp64 sum lands within 2^-29 relative of an fp32 tie) -- it only chooses the start
-cell. On the device the authority for that is shacira_raytrace_dense itself, which tests/test_gpu_spc.py compares against."""
+The walk and the first hit. ``walk_ref`` is the slab test and the Amanatides-Woo walk of shacira_raytrace_dense in numpy float32
+scalars: every occupied cell whose stay has positive length, in depth order; ``first_hit_ref``, "the first nugget of a flat fp32
+DDA", is its first nugget per finite ray. The one fused operation of the walk's set-up, fmaf(d, tin, o), is evaluated in fp64 and
+rounded to fp32 (the product is exact in fp64; the sum rounds twice, which can differ from the fused result only when the fp64
+sum lands within 2^-29 relative of an fp32 tie) -- it only chooses the start cell. The authority is what the device computed:
+tests/golden/grid_walk.npz, which tests/test_spc_cpu.py holds this restatement to, bit for bit."""
 import numpy as np
 import torch
 
@@ -81,6 +82,16 @@ def words_ref(keys, level):
     return words
 
 
+def occupancy_bits(occupancy):
+    """bool [G, G, G] -> uint8 bytes: cell key is bit key & 7 of byte key >> 3 -- the bytes of the packed words, unpadded."""
+    return np.packbits(np.asarray(occupancy, bool).reshape(-1), bitorder="little")
+
+
+def occupancy_from_bits(bits, level):
+    G = 1 << level
+    return np.unpackbits(np.asarray(bits, np.uint8), count=G ** 3, bitorder="little").astype(bool).reshape(G, G, G)
+
+
 def popcount(words):
     w = np.asarray(words, np.uint32).astype(np.int64)
     return sum((w >> b) & 1 for b in range(32))
@@ -121,17 +132,19 @@ def _fma32(a, b, c):
     return F32(np.float64(a) * np.float64(b) + np.float64(c))
 
 
-def first_hit_ref(origins, dirs, occupancy, level):
-    """origins, dirs fp32 [N, 3]; occupancy bool [G, G, G] indexed [x][y][z]. -> (depth fp32 [N], hit bool [N], pidx int32 [N])."""
+def walk_ref(origins, dirs, occupancy, level, finite_gate, first=False):
+    """origins, dirs fp32 [N, 3]; occupancy bool [G, G, G] indexed [x][y][z]. -> every nugget, in ray and then depth order:
+    (ridx int32 [K], cells int32 [K, 3], depth fp32 [K, 2] = t_enter, t_exit). ``finite_gate``: a ray with a component that is
+    not finite has no nugget (shacira_spc_first_hit's contract; shacira_raytrace_dense has no such gate). ``first``: a ray's
+    walk stops after its first nugget."""
     G = 1 << level
     origins, dirs = np.asarray(origins, F32), np.asarray(dirs, F32)
-    N = origins.shape[0]
-    depth, hit, pidx = np.zeros(N, F32), np.zeros(N, bool), np.full(N, -1, np.int32)
+    ridx, cells, depth = [], [], []
     inf, one, zero = F32(np.inf), F32(1.0), F32(0.0)
     with np.errstate(all="ignore"):
-        for r in range(N):
+        for r in range(origins.shape[0]):
             o, d = origins[r], dirs[r]
-            if not (np.isfinite(o).all() and np.isfinite(d).all()):
+            if finite_gate and not (np.isfinite(o).all() and np.isfinite(d).all()):
                 continue
             tn, tf, miss = -inf, inf, False
             for a in range(3):
@@ -161,8 +174,9 @@ def first_hit_ref(origins, dirs, occupancy, level):
                 a = (0 if tmax[0] <= tmax[2] else 2) if tmax[0] <= tmax[1] else (1 if tmax[1] <= tmax[2] else 2)
                 texit = min(tmax[a], tf)
                 if texit > t and occupancy[c[0], c[1], c[2]]:
-                    depth[r], hit[r], pidx[r] = t, True, morton(c[0], c[1], c[2], level)
-                    break
+                    ridx.append(r), cells.append(tuple(c)), depth.append((t, texit))
+                    if first:
+                        break
                 t = max(t, texit)
                 if tmax[a] >= tf:
                     break
@@ -170,4 +184,15 @@ def first_hit_ref(origins, dirs, occupancy, level):
                 if c[a] < 0 or c[a] >= G:
                     break
                 tmax[a] = F32(tmax[a] + tdelta[a])
+    return (np.array(ridx, np.int32), np.array(cells, np.int32).reshape(-1, 3), np.array(depth, F32).reshape(-1, 2))
+
+
+def first_hit_ref(origins, dirs, occupancy, level):
+    """origins, dirs fp32 [N, 3]; occupancy bool [G, G, G] indexed [x][y][z]. -> (depth fp32 [N], hit bool [N], pidx int32 [N]):
+    the first nugget of every finite ray that has one."""
+    N = np.asarray(origins).shape[0]
+    depth, hit, pidx = np.zeros(N, F32), np.zeros(N, bool), np.full(N, -1, np.int32)
+    ridx, cells, t = walk_ref(origins, dirs, occupancy, level, finite_gate=True, first=True)
+    depth[ridx], hit[ridx] = t[:, 0], True
+    pidx[ridx] = [morton(int(x), int(y), int(z), level) for x, y, z in cells]
     return depth, hit, pidx

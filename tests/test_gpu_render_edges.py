@@ -363,6 +363,18 @@ def _special_rays():
     return rays
 
 
+def _trace_rays(N, level, seed):
+    """N rays towards the cube, the special ones first (tests/golden/make_grid_walk.py records the same rays)."""
+    rng = np.random.default_rng(seed)
+    o, d = _rays(rng, N)
+    if level == 8:                                       # every sixth ray aims at the occupied block in the centre
+        ob, db = _rays(rng, N, aim=1.0 / 16)
+        o[::6], d[::6] = ob[::6], db[::6]
+    for k, (so, sd) in enumerate(_special_rays()[:N]):
+        o[k], d[k] = torch.tensor(so), torch.tensor(sd)
+    return o, d
+
+
 @pytest.mark.parametrize("N,level,seed", [(1, 0, 300), (1, 8, 300), (255, 1, 300), (256, 3, 300), (257, 8, 303), (600, 3, 300),
                                           (600, 0, 300)])
 def test_raytrace_dense_ragged_sizes_levels_and_special_rays(dev, N, level, seed):
@@ -373,13 +385,7 @@ def test_raytrace_dense_ragged_sizes_levels_and_special_rays(dev, N, level, seed
     walk adds a cell's length to its exit depth at every step, and after 128 steps at level 8 an interval's length is up to
     1.2e-5 off -- so the rule cannot split the two sides."""
     from shacira_amd import _lib, render
-    rng = np.random.default_rng(seed)
-    o, d = _rays(rng, N)
-    if level == 8:                                       # every sixth ray aims at the occupied block in the centre
-        ob, db = _rays(rng, N, aim=1.0 / 16)
-        o[::6], d[::6] = ob[::6], db[::6]
-    for k, (so, sd) in enumerate(_special_rays()[:N]):
-        o[k], d[k] = torch.tensor(so), torch.tensor(sd)
+    o, d = _trace_rays(N, level, seed)
     occ = _trace_occupancy(level)
     ridx, pidx, depth = [t.cpu() for t in render.raytrace_dense(o.to(dev), d.to(dev), occ.to(dev), level)]
     # the count pass agrees with the emit pass

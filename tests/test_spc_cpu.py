@@ -77,6 +77,32 @@ def test_first_hit_by_hand():
     assert (depth[0], hit[0], pidx[0]) == (1.0, True, 7)
 
 
+def test_walk_restatement_equals_the_recorded_kernels():
+    """tests/golden/grid_walk.npz holds what the dense-grid walk computed on an MI355X (tests/golden/make_grid_walk.py):
+    ``walk_ref`` and ``first_hit_ref`` reproduce it on the recorded inputs -- counts, ray ids and Morton indices exactly, every
+    depth bit for bit. The recording is the authority; tests/test_gpu_grid_walk.py holds the kernels to the same file."""
+    import os
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grid_walk.npz"))
+    dense = sorted({tuple(k.split(".")[1:3]) for k in gold.files if k.startswith("dense.")})
+    assert len(dense) == 6
+    for N, level in dense:
+        g = lambda name: gold[f"dense.{N}.{level}.{name}"]
+        level = int(level)
+        occ = S.occupancy_from_bits(g("bits"), level)
+        ridx, cells, depth = S.walk_ref(g("origins"), g("dirs"), occ, level, finite_gate=False)
+        assert np.array_equal(np.bincount(ridx, minlength=int(N)), g("counts")) and np.array_equal(ridx, g("ridx"))
+        assert np.array_equal([S.morton(int(x), int(y), int(z), level) for x, y, z in cells], g("pidx"))
+        assert np.array_equal(depth.view(np.int32), g("depth").view(np.int32))
+    hits = sorted({tuple(k.split(".")[1:4]) for k in gold.files if k.startswith("hit.") and k.endswith(".origins")})
+    assert len(hits) == 3 * 5 * 5
+    for level, kind, N in hits:
+        g = lambda name: gold[f"hit.{level}.{kind}.{N}.{name}"]
+        occ = S.occupancy_from_bits(gold[f"hit.{level}.{kind}.bits"], int(level))
+        depth, hit, pidx = S.first_hit_ref(g("origins"), g("dirs"), occ, int(level))
+        assert np.array_equal(hit, g("hit")) and np.array_equal(pidx, g("pidx")), (level, kind, N)
+        assert np.array_equal(depth.view(np.int32), g("depth").view(np.int32)), (level, kind, N)
+
+
 # ---- wisp.ops.pointcloud and the camera moves --------------------------------------------------------------------------------
 def test_create_pointcloud_from_images_literal():
     rgb = torch.arange(2 * 2 * 4, dtype=torch.float32).reshape(2, 2, 4)

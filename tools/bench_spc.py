@@ -10,6 +10,8 @@ distance 3, depth along this package's own rays, colours from the hit point, bac
     ``index_add_``). Peak device bytes of one call of each, above what is resident before it.
 (b) First hit of ``--rays`` squared rays of a further camera: ``hip_ops.spc_first_hit`` (one launch) against
     ``PackedSPCTracer.trace_composed`` (every crossing emitted, the first of each ray marked, colours gathered, four scatters).
+(c) ``render.raytrace_dense`` alone (count, scan, emit) on the rays of (b): the other visitor of the walk of ``grid_walk.h``,
+    which (b) times only under the torch glue of ``trace_composed``. Windows of the same length, no second leg.
 Every round times leg A, leg B and leg A again, each a window of back-to-back calls between device events after a warm-up of every
 shape; the report gives min / median / max over the rounds, so the spread of a leg against itself is known before two legs are
 compared. The outputs of the two legs are compared before anything is timed. No coarse "empty brick" bit was tried in the
@@ -25,7 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from shacira_amd import hip_ops  # noqa: E402
+from shacira_amd import hip_ops, render  # noqa: E402
 from shacira_amd.wisp.core import Camera, Rays  # noqa: E402
 from shacira_amd.wisp.models.nefs import SPCField  # noqa: E402
 from shacira_amd.wisp.ops.raygen import camera_records  # noqa: E402
@@ -216,6 +218,25 @@ def main():
     say()
     pt, pm = _peak(one, dev), _peak(many, dev)
     say(f"Peak device bytes of one call: fused {pt / 1e6:.1f} MB, composed {pm / 1e6:.1f} MB.")
+    say()
+
+    # ---- (c) the dense trace alone
+    occ = nef.grid.blas.occupancy_at(L, dev)
+    dense = lambda: render.raytrace_dense(o, d, occ, L)
+    nuggets = dense()[0].shape[0]
+    dense()
+    dn = [_window(dense, 100) for _ in range(2 * args.samples)]
+    say("## (c) `render.raytrace_dense` alone on the rays of (b)")
+    say()
+    say(f"{nuggets} nuggets. Count launch, scan (with the read-back of the total that sizes the outputs) and emit launch: what "
+        "`trace_composed` spends before its torch glue. Two windows a round, as many as the fused leg of (b).")
+    say()
+    say("| leg | us per call |")
+    say("|---|---|")
+    say(f"| `render.raytrace_dense` | {_fmt(dn)} |")
+    say()
+    say(f"Medians (us): `spc_first_hit` {statistics.median(t1 + t2):.1f} | `trace_composed` {statistics.median(m):.1f} | "
+        f"`raytrace_dense` {statistics.median(dn):.1f}")
     say()
     say("## Register counts (gfx950 code objects, `llvm-readelf --notes`)")
     say()
