@@ -1407,6 +1407,37 @@ SHACIRA_API int shacira_raytrace_dense_count(int64_t num_rays, const float *orig
 SHACIRA_API int shacira_raytrace_dense_emit(int64_t num_rays, const float *origins, const float *dirs,
                                 const uint8_t *occupancy, int level, const int64_t *offsets, int32_t *ridx,
                                 int32_t *pidx, float *depth, void *stream);
+/*
+ * The 'voxel' marcher (ABI 11, additive): `num_samples` jittered samples inside every occupied crossing, the jitter restated
+ * from a seed. Counting is shacira_raytrace_dense_count; the caller scans the counts into `offsets` int64 [num_rays + 1] (in
+ * NUGGETS); a ray with c crossings owns the c * num_samples rows from offsets[r] * num_samples on.
+ *   nuggets   nugget i of ray r is the i-th crossing shacira_raytrace_dense_emit writes for that ray on the same occupancy,
+ *             (t0, t1) bit for bit (the one walk of grid_walk.h).
+ *   rows      ordered by ray, nugget, j < num_samples. With u the jitter below and every operator rounded to fp32 on its
+ *             own (no fma; 1.0f / num_samples is the fp32 value of the double quotient):
+ *               depth    = t0 + (t1 - t0) * ((float(j) + u) * (1.0f / num_samples))
+ *               deltas   = depth - depth of row j - 1 of the SAME nugget, t0 before the first (it restarts at every nugget)
+ *               samples  = fmaf(dir, depth, origin) per axis
+ *               ridx     = r (int64); boundary (uint8) = 1 on row j == 0 of the ray's first nugget, else 0
+ *   jitter    u = (w >> 8) * 2^-24 in [0, 1), w = word (j & 3) of Philox4x32-10 with
+ *               counter = (c0, c1, c2, c3) = (r, i, j >> 2, low 32 bits of (step + *step_dev))
+ *               key     = (k0, k1)         = (low, high 32 bits of seed)
+ *             so a sample's jitter depends on (seed, step, r, i, j) only: not on its row, on the capacity or on the other
+ *             rays. `step_dev` (device int64, may be NULL = 0) is read when the kernel runs: a captured graph that
+ *             increments it draws fresh jitter on every replay. num_rays >= 2^32 is SHACIRA_EINVAL.
+ *   capacity  rows of the output buffers; rows >= capacity are dropped, even in the middle of a nugget, the rows behind the
+ *             last survivor are left untouched and the caller clamps its row offsets (the contract of
+ *             shacira_raymarch_ray_emit_capped). The uncapped call passes capacity = offsets[num_rays] * num_samples.
+ *   workspace shacira_raymarch_voxel_workspace_bytes(capacity, num_samples) bytes (the compact nuggets: a thread per ray
+ *             walks and writes them, a thread per row expands them), else SHACIRA_EWORKSPACE.
+ * num_rays == 0 or capacity == 0 launches nothing and returns 0. num_samples in 1 .. 2^24.
+ */
+SHACIRA_API size_t shacira_raymarch_voxel_workspace_bytes(int64_t capacity, int num_samples);
+SHACIRA_API int shacira_raymarch_voxel_emit(int64_t num_rays, int num_samples, const float *origins, const float *dirs,
+                                const uint8_t *occupancy, int level, const int64_t *offsets, uint64_t seed, int64_t step,
+                                const int64_t *step_dev, int64_t capacity, void *workspace, size_t workspace_bytes,
+                                int64_t *ridx, float *samples, float *depth, float *deltas, uint8_t *boundary,
+                                void *stream);
 
 /*
  * Sphere tracing over ray packs (ABI 11, additive): the reference's `find_depth_bound_cuda`

@@ -154,6 +154,9 @@ SIGNATURES = {
     "shacira_raymarch_ray_emit_capped": (_i, [_i64, _i, _p, _p, _f, _f, _p, _p, _p, _i, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "shacira_raytrace_dense_count": (_i, [_i64, _p, _p, _p, _i, _p, _p]),
     "shacira_raytrace_dense_emit": (_i, [_i64, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "shacira_raymarch_voxel_workspace_bytes": (_sz, [_i64, _i]),
+    "shacira_raymarch_voxel_emit": (_i, [_i64, _i, _p, _p, _p, _i, _p, ctypes.c_uint64, _i64, _p, _i64, _p, _sz, _p, _p, _p,
+                                         _p, _p, _p]),
     "shacira_mlp_supported": (_i, [_i, _i, _i, _i]),
     "shacira_mlp_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "shacira_mlp_forward": (_i, [_i64, _i, _i, _i, _i, _p, _p, _p, _p]),

@@ -1509,6 +1509,31 @@ int shacira_raytrace_dense_emit(int64_t num_rays, const float *origins, const fl
                                       depth, (hipStream_t)stream);
 }
 
+// rows of `capacity` belong to ceil(capacity / num_samples) nuggets of (ray uint32, entry fp32, exit fp32)
+static bool voxel_sizes_ok(int64_t capacity, int num_samples) {
+    return num_samples >= 1 && num_samples <= (1 << 24) && capacity >= 0 && capacity <= (int64_t)1 << 38;
+}
+
+size_t shacira_raymarch_voxel_workspace_bytes(int64_t capacity, int num_samples) {
+    if (!voxel_sizes_ok(capacity, num_samples)) return 0;
+    return (size_t)((capacity + num_samples - 1) / num_samples) * 12;
+}
+
+int shacira_raymarch_voxel_emit(int64_t num_rays, int num_samples, const float *origins, const float *dirs,
+                                const uint8_t *occupancy, int level, const int64_t *offsets, uint64_t seed, int64_t step,
+                                const int64_t *step_dev, int64_t capacity, void *workspace, size_t workspace_bytes,
+                                int64_t *ridx, float *samples, float *depth, float *deltas, uint8_t *boundary,
+                                void *stream) {
+    if (int rc = march_args_ok(num_rays, origins, dirs, occupancy, level)) return rc;
+    if (num_rays >= (int64_t)1 << 32 || !voxel_sizes_ok(capacity, num_samples)) return SHACIRA_EINVAL;
+    if (num_rays == 0 || capacity == 0) return 0;
+    if (!offsets || !ridx || !samples || !depth || !deltas || !boundary) return SHACIRA_EINVAL;
+    if (!workspace || workspace_bytes < shacira_raymarch_voxel_workspace_bytes(capacity, num_samples))
+        return SHACIRA_EWORKSPACE;
+    return (int)raymarch_voxel_launch(num_rays, num_samples, origins, dirs, occupancy, level, offsets, seed, step, step_dev,
+                                      capacity, workspace, ridx, samples, depth, deltas, boundary, (hipStream_t)stream);
+}
+
 size_t shacira_entropy_bits_workspace_bytes(int64_t, int) { return latent_workspace_bytes(); }
 
 int shacira_entropy_bits_forward(int64_t num_rows, int latent_dim, int num_layers, const float *latent,

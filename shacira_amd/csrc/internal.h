@@ -365,6 +365,10 @@ hipError_t raymarch_ray_launch(bool emit, int64_t num_rays, int ns, const float 
 hipError_t raytrace_dense_launch(bool emit, int64_t num_rays, const float *origins, const float *dirs,
                                  const uint8_t *occ, int level, int32_t *counts, const int64_t *offsets, int32_t *ridx,
                                  int32_t *pidx, float *depth, hipStream_t s);
+hipError_t raymarch_voxel_launch(int64_t num_rays, int ns, const float *origins, const float *dirs, const uint8_t *occ,
+                                 int level, const int64_t *offsets, uint64_t seed, int64_t step, const int64_t *step_dev,
+                                 int64_t capacity, void *workspace, int64_t *ridx, float *samples, float *depth,
+                                 float *deltas, uint8_t *boundary, hipStream_t s);
 
 // probe.hip
 hipError_t stream_probe_launch(int kind, const void *a, void *b, size_t bytes, uint32_t *sink, hipStream_t s);

@@ -10,6 +10,7 @@
 // chunks of 64 samples: loads are coalesced, the running optical depth is a wave scan plus a carry.
 #include "grid_walk.h"
 #include "internal.h"
+#include "philox.h"
 
 namespace shacira {
 
@@ -273,6 +274,73 @@ __global__ __launch_bounds__(256) void raytrace_dense_kernel(int64_t num_rays, c
     if constexpr (!EMIT) counts[r] = n;
 }
 
+// 'voxel' marcher (octree_as.py:171-233), seeded: `ns` jittered samples inside every occupied crossing. Two passes over the
+// scanned counts of raytrace_dense_kernel<false>. Pass 1, thread per ray: the walk again, writing the compact nuggets (ray,
+// entry, exit) of the rays into the caller's workspace; a nugget whose index is >= nug_cap has no row below the capacity and
+// is dropped.
+__global__ __launch_bounds__(256) void raymarch_voxel_nuggets_kernel(int64_t num_rays, const float *__restrict__ origins,
+                                                                     const float *__restrict__ dirs,
+                                                                     const uint8_t *__restrict__ occ, int level,
+                                                                     const int64_t *__restrict__ offsets, int64_t nug_cap,
+                                                                     uint32_t *__restrict__ nug_ray,
+                                                                     float *__restrict__ nug_t0, float *__restrict__ nug_t1) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= num_rays) return;
+    const int G = 1 << level;
+    int64_t out = offsets[r];
+    if (out >= nug_cap) return;
+    grid_walk(origins[r * 3], origins[r * 3 + 1], origins[r * 3 + 2], dirs[r * 3], dirs[r * 3 + 1], dirs[r * 3 + 2], level,
+              [&](int cx, int cy, int cz, float t, float texit) {
+                  if (!occupied(occ, G, cx, cy, cz)) return false;
+                  nug_ray[out] = (uint32_t)r;
+                  nug_t0[out] = t;
+                  nug_t1[out] = texit;
+                  return ++out >= nug_cap;
+              });
+}
+
+// the jitter of sample j of nugget i of ray r: word j & 3 of Philox4x32-10 on counter (r, i, j >> 2, step), key = seed
+__device__ __forceinline__ float voxel_jitter(uint32_t r, uint32_t i, uint32_t j, uint32_t step, uint32_t k0, uint32_t k1) {
+    uint32_t w[4];
+    philox4x32_10(r, i, j >> 2, step, k0, k1, w);
+    const uint32_t lo = (j & 1u) ? w[1] : w[0], hi = (j & 1u) ? w[3] : w[2];      // selects: no private segment
+    return unit_open_above((j & 2u) ? hi : lo);
+}
+
+// depth of sample j between t0 and t1, every operator rounded to fp32 on its own (sampling.py:49-55 runs them as separate
+// torch operators; hipcc would contract the last two into an fma)
+__device__ __forceinline__ float voxel_depth(float t0, float t1, uint32_t j, float u, float inv_ns) {
+    return __fadd_rn(t0, __fmul_rn(__fsub_rn(t1, t0), __fmul_rn(__fadd_rn((float)j, u), inv_ns)));
+}
+
+// Pass 2, thread per output row (row = nugget * ns + j): consecutive lanes write consecutive rows of every output.
+__global__ __launch_bounds__(256) void raymarch_voxel_expand_kernel(
+    int64_t num_rays, int ns, float inv_ns, const float *__restrict__ origins, const float *__restrict__ dirs,
+    const int64_t *__restrict__ offsets, const uint32_t *__restrict__ nug_ray, const float *__restrict__ nug_t0,
+    const float *__restrict__ nug_t1, uint32_t k0, uint32_t k1, int64_t step, const int64_t *__restrict__ step_dev,
+    int64_t capacity, int64_t *__restrict__ ridx, float *__restrict__ samples, float *__restrict__ depth_out,
+    float *__restrict__ deltas, uint8_t *__restrict__ boundary) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= capacity) return;
+    const int64_t k = row / ns;
+    if (k >= offsets[num_rays]) return;                      // behind the last nugget: the row is left untouched
+    const uint32_t j = (uint32_t)(row - k * ns);
+    const int64_t r = nug_ray[k];
+    if (r >= num_rays) return;
+    const uint32_t i = (uint32_t)(k - offsets[r]);
+    const uint32_t st = (uint32_t)(uint64_t)(step + (step_dev ? *step_dev : 0));
+    const float t0 = nug_t0[k], t1 = nug_t1[k];
+    const float depth = voxel_depth(t0, t1, j, voxel_jitter((uint32_t)r, i, j, st, k0, k1), inv_ns);
+    const float prev = j == 0 ? t0 : voxel_depth(t0, t1, j - 1, voxel_jitter((uint32_t)r, i, j - 1, st, k0, k1), inv_ns);
+    ridx[row] = r;
+    samples[row * 3] = fmaf(dirs[r * 3], depth, origins[r * 3]);
+    samples[row * 3 + 1] = fmaf(dirs[r * 3 + 1], depth, origins[r * 3 + 1]);
+    samples[row * 3 + 2] = fmaf(dirs[r * 3 + 2], depth, origins[r * 3 + 2]);
+    depth_out[row] = depth;
+    deltas[row] = __fsub_rn(depth, prev);
+    boundary[row] = (i == 0 && j == 0) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------------ host side
 static inline uint32_t pack_blocks(int64_t R) { return (uint32_t)((R + kPackWaves - 1) / kPackWaves); }
 
@@ -338,6 +406,23 @@ hipError_t raytrace_dense_launch(bool emit, int64_t num_rays, const float *origi
     else
         hipLaunchKernelGGL(raytrace_dense_kernel<true>, grid, block, 0, s, num_rays, origins, dirs, occ, level, counts,
                            offsets, ridx, pidx, depth);
+    return hipGetLastError();
+}
+
+hipError_t raymarch_voxel_launch(int64_t num_rays, int ns, const float *origins, const float *dirs, const uint8_t *occ,
+                                 int level, const int64_t *offsets, uint64_t seed, int64_t step, const int64_t *step_dev,
+                                 int64_t capacity, void *workspace, int64_t *ridx, float *samples, float *depth,
+                                 float *deltas, uint8_t *boundary, hipStream_t s) {
+    if (num_rays == 0 || capacity == 0) return hipSuccess;
+    const int64_t nug_cap = (capacity + ns - 1) / ns;
+    uint32_t *nug_ray = (uint32_t *)workspace;
+    float *nug_t0 = (float *)(nug_ray + nug_cap), *nug_t1 = nug_t0 + nug_cap;
+    hipLaunchKernelGGL(raymarch_voxel_nuggets_kernel, dim3((uint32_t)((num_rays + 255) / 256)), dim3(256), 0, s, num_rays,
+                       origins, dirs, occ, level, offsets, nug_cap, nug_ray, nug_t0, nug_t1);
+    const float inv_ns = (float)(1.0 / (double)ns);          // the fp32 value of Python's 1.0 / num_samples
+    hipLaunchKernelGGL(raymarch_voxel_expand_kernel, dim3((uint32_t)((capacity + 255) / 256)), dim3(256), 0, s, num_rays, ns,
+                       inv_ns, origins, dirs, offsets, nug_ray, nug_t0, nug_t1, (uint32_t)seed, (uint32_t)(seed >> 32), step,
+                       step_dev, capacity, ridx, samples, depth, deltas, boundary);
     return hipGetLastError();
 }
 

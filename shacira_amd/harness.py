@@ -694,7 +694,10 @@ class GraphedNerfFitter:
     * the batch comes from a pool of rays with their target colours resident on the device (the role of the reference's
       MultiviewDataset: rays + pixels of the training images), indexed by a step counter kept on the device; Adam keeps its
       step count on the device too (FusedAdam(capturable=True)).
-    A graph is re-captured when a prune changes the capacity (a few times per run)."""
+    A graph is re-captured when a prune changes the capacity (a few times per run).
+    The marcher is the tracer's: 'ray', or the seeded 'voxel' march (`PackedRFTracer(raymarch_type="voxel", seed=...)`, capped by
+    `shacira_raymarch_voxel_emit`), whose step counter is a device int64 this class owns, hands to the tracer and increments
+    inside the step, so that every replay draws new jitter."""
 
     def __init__(self, nef, tracer, groups, pool, near, far, device, margin=1.08, quantum=16384, latent=None):
         from .optim import FusedAdam
@@ -719,6 +722,14 @@ class GraphedNerfFitter:
         # SGA is switched off (after decay_period of the run) the graphs are dropped and re-captured once.
         self.latent = latent
         self.iteration = 0
+        # the seeded 'voxel' march tells its calls apart by a step: kept on the device, so that every replay draws new jitter
+        self.march_step = None
+        if tracer.raymarch_type == "voxel":
+            if tracer.seed is None:
+                raise ValueError("GraphedNerfFitter: the 'voxel' march is captured only in its seeded form "
+                                 "(PackedRFTracer(seed=...))")
+            self.march_step = torch.zeros(1, dtype=torch.int64, device=device)
+            tracer.step = self.march_step
         self.extra_eager_steps = 0      # optimizer steps taken by prepare()'s shape warm-ups (reported, see fit_nerf)
         if latent is not None:
             _require_device_temperature(nef.grid.latent_dec, "GraphedNerfFitter")
@@ -746,6 +757,8 @@ class GraphedNerfFitter:
         self.opt.step()
         self.loss.copy_(loss.detach())
         self.index.add_(1).remainder_(self.pool_o.shape[0])
+        if self.march_step is not None:
+            self.march_step.add_(1)
         if self.capacity is not None:
             self.overflow.add_((self.blas.last_sample_count > self.capacity).to(torch.int64))
 
@@ -757,7 +770,9 @@ class GraphedNerfFitter:
         with torch.no_grad():
             for j in range(probes):
                 batch, _ = self._batch((j * 7919) % P)
-                m = self.nef.grid.raymarch(batch, level=None, num_samples=self.tracer.num_steps, raymarch_type="ray")
+                kind = self.tracer.raymarch_type
+                seeded = dict(seed=self.tracer.seed) if kind == "voxel" else {}      # the count does not depend on the jitter
+                m = self.nef.grid.raymarch(batch, level=None, num_samples=self.tracer.num_steps, raymarch_type=kind, **seeded)
                 need = max(need, m.samples.shape[0])
         return int(-(-int(need * self.margin) // self.quantum) * self.quantum)
 
@@ -826,11 +841,13 @@ class GraphedNerfFitter:
 
 def fit_nerf(device, steps=300, rays=4096, num_steps=128, seed=0, codebook_bitwidth=19, max_grid_res=2048,
              num_lods=16, blas_level=5, prune_every=100, val_rays=8192, hidden_dim=64, latent=False,
-             entropy_reg=1.0e-4, feature_dim=2, graphed=False, ray_pool=0):
+             entropy_reg=1.0e-4, feature_dim=2, graphed=False, ray_pool=0, raymarch_type="ray"):
     """NeRF-style fit of the analytic scene through the full pipeline the reference runs per step
     (multiview_trainer.py:88-150): ray marching on the occupancy grid ('ray' sampler) -> hash-grid lookup -> density /
     colour decoders -> volume integration -> L1 to the target pixels -> Adam; occupancy pruned every `prune_every` steps.
     Targets are rendered from the closed-form scene by the same tracer with 4x the samples.
+    `raymarch_type="voxel"`: the fused seeded voxel march (`num_steps` samples inside every crossed cell, jitter from `seed` and
+    the step count) for the fit, its targets (4x the samples per cell) and the validation render.
     `latent=True`: the compressed variant the reference's nerf_lego.yaml trains -- a 3-D LatentGrid (latent_dim 1, SGA
     warm-up with temperature 1.0 until decay_period 0.9, entropy model with one layer, lambda = `entropy_reg`); the
     result then also carries the size estimate and the bytes of the entropy-coded model file. nerf_lego.yaml's shape is
@@ -874,8 +891,12 @@ def fit_nerf(device, steps=300, rays=4096, num_steps=128, seed=0, codebook_bitwi
     truth = _AnalyticNef(HashGrid.from_geometric(feature_dim=2, num_lods=2, multiscale_type="cat", resolution_dim=3,
                                                  feature_std=0.0, codebook_bitwidth=4, min_grid_res=2,
                                                  max_grid_res=4, blas_level=blas_level))   # carries the occupancy only
-    tracer = PackedRFTracer(raymarch_type="ray", num_steps=num_steps, bg_color="white")
-    gt_tracer = PackedRFTracer(raymarch_type="ray", num_steps=4 * num_steps, bg_color="white")
+    if raymarch_type not in ("ray", "voxel"):
+        raise ValueError(f"fit_nerf: raymarch_type {raymarch_type!r} is neither 'ray' nor 'voxel'")
+    march_seed = seed if raymarch_type == "voxel" else None
+    tracer = PackedRFTracer(raymarch_type=raymarch_type, num_steps=num_steps, bg_color="white", seed=march_seed)
+    gt_tracer = PackedRFTracer(raymarch_type=raymarch_type, num_steps=4 * num_steps, bg_color="white",
+                               seed=None if march_seed is None else march_seed + 1)
     groups = [g for g in param_groups(nef, lr=1e-3, grid_lr=1e-2) if g["params"]]
     near, far = 1.2, 4.8
     warm = min(20, steps // 10)          # first steps pay one-off costs (kernel attribute set-up, allocator growth)
@@ -1060,10 +1081,11 @@ def evaluate_view(nef, tracer, dataset, i, chunk=4096):
 
 
 def fit_multiview(dataset, device, steps=300, rays=4096, num_steps=128, seed=0, codebook_bitwidth=19, max_grid_res=2048,
-                  num_lods=16, blas_level=5, prune_every=100, hidden_dim=64, feature_dim=2):
+                  num_lods=16, blas_level=5, prune_every=100, hidden_dim=64, feature_dim=2, raymarch_type="ray"):
     """The eager step of ``fit_nerf`` fed by a multiview dataset: every step draws ``rays`` random pixels over all views with
     ``dataset.sample`` -- rays and composited target colours made on the device by the ray kernel -- renders them through the
-    hash grid and takes an L1 / Adam step. Returns dict(nef, tracer, losses [steps] on the host, ms_per_step)."""
+    hash grid and takes an L1 / Adam step; `raymarch_type="voxel"` marches with the fused seeded voxel march (`num_steps` samples
+    inside every crossed cell). Returns dict(nef, tracer, losses [steps] on the host, ms_per_step)."""
     import time
     from .optim import FusedAdam
     from .wisp.models.grids import HashGrid
@@ -1075,7 +1097,10 @@ def fit_multiview(dataset, device, steps=300, rays=4096, num_steps=128, seed=0, 
                                    max_grid_res=max_grid_res, blas_level=blas_level)
     nef = NeuralRadianceField(grid, view_embedder="positional", view_multires=4, hidden_dim=hidden_dim, num_layers=1,
                               prune_density_decay=0.95, prune_min_density=0.01 * 512 / 3 ** 0.5).to(device)
-    tracer = PackedRFTracer(raymarch_type="ray", num_steps=num_steps, bg_color=dataset.bg_color)
+    if raymarch_type not in ("ray", "voxel"):
+        raise ValueError(f"fit_multiview: raymarch_type {raymarch_type!r} is neither 'ray' nor 'voxel'")
+    tracer = PackedRFTracer(raymarch_type=raymarch_type, num_steps=num_steps, bg_color=dataset.bg_color,
+                            seed=seed if raymarch_type == "voxel" else None)
     opt = FusedAdam([g for g in param_groups(nef, lr=1e-3, grid_lr=1e-2) if g["params"]], eps=1e-15)
     gen = torch.Generator(device=device).manual_seed(seed + 1)
     losses = []

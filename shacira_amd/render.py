@@ -177,6 +177,58 @@ def raymarch_ray(origins, dirs, dist_min, dist_max, occupancy, level, num_sample
     return ridx, samples, depth, deltas, boundary.bool(), offsets
 
 
+def raymarch_voxel(origins, dirs, occupancy, level, num_samples, seed, step=0, capacity=None):
+    """`OctreeAS._raymarch_voxel` (reference octree_as.py:171-233) fused and seeded: ``num_samples`` jittered samples inside
+    every crossing of an occupied cell of the dense grid [G, G, G] (bool, [x][y][z]), the nuggets of `raytrace_dense`, in
+    three launches (count, nuggets, expand) and one count read-back; the jitter is restated from ``(seed, step, ray, nugget,
+    sample)`` (the contract above ``shacira_raymarch_voxel_emit``). ``step`` is an int or a device int64 tensor of one
+    element, read when the kernel runs. Returns what `raymarch_ray` returns: ridx int64 [S], samples [S, 3], depth_samples
+    [S, 1], deltas [S, 1], boundary bool [S], per-ray pack offsets int64 [num_rays + 1]; with ``capacity`` no count is read
+    back, the outputs have ``capacity`` rows (padding behind the last survivor), the offsets are clamped and the true row
+    count follows as a device int64 scalar."""
+    _need_gpu(origins, dirs, occupancy)
+    origins, dirs = origins.float().contiguous(), dirs.float().contiguous()
+    N, dev, ns = origins.shape[0], origins.device, int(num_samples)
+    occ = _occupancy_u8(occupancy, level)
+    step_dev = None
+    if torch.is_tensor(step):
+        _need_gpu(step)
+        if step.dtype != torch.int64 or step.numel() != 1:
+            raise RuntimeError("raymarch_voxel: a tensor step must be one int64 element")
+        step, step_dev = 0, step
+    L = _lib.lib()
+    with _on_device(dev):
+        counts = torch.empty((N,), dtype=torch.int32, device=dev)
+        _lib.check(L.shacira_raytrace_dense_count(N, _ptr(origins), _ptr(dirs), _ptr(occ), int(level), _ptr(counts),
+                                                  _stream(origins)), "shacira_raytrace_dense_count")
+        nuggets = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=nuggets[1:])
+        offsets = nuggets * ns
+        if capacity is not None:
+            S = int(capacity)
+            ridx = torch.zeros((S,), dtype=torch.int64, device=dev)
+            samples = _padding_positions(S, dev).clone()     # rows behind the last survivor keep these
+            depth = torch.zeros((S, 1), dtype=torch.float32, device=dev)
+            deltas = torch.zeros((S, 1), dtype=torch.float32, device=dev)
+            boundary = torch.zeros((S,), dtype=torch.bool, device=dev)     # one byte a row: the kernel stores 0 / 1
+        else:
+            S = int(nuggets[-1].item()) * ns
+            ridx = torch.empty((S,), dtype=torch.int64, device=dev)
+            samples = torch.empty((S, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((S, 1), dtype=torch.float32, device=dev)
+            deltas = torch.empty((S, 1), dtype=torch.float32, device=dev)
+            boundary = torch.empty((S,), dtype=torch.bool, device=dev)
+        ws_bytes = int(L.shacira_raymarch_voxel_workspace_bytes(S, ns))
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        _lib.check(L.shacira_raymarch_voxel_emit(N, ns, _ptr(origins), _ptr(dirs), _ptr(occ), int(level), _ptr(nuggets),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _ptr(step_dev), S, _ptr(ws),
+                                                 ws_bytes, _ptr(ridx), _ptr(samples), _ptr(depth), _ptr(deltas),
+                                                 _ptr(boundary), _stream(origins)), "shacira_raymarch_voxel_emit")
+    if capacity is not None:
+        return ridx, samples, depth, deltas, boundary, offsets.clamp(max=S), offsets[-1].clone()
+    return ridx, samples, depth, deltas, boundary, offsets
+
+
 def raytrace_dense(origins, dirs, occupancy, level):
     """Ray / occupied-cell intersections in depth order (stands in for kaolin's unbatched_raytrace(with_exit=True) on a
     one-level dense octree): ridx int32 [K], pidx int32 [K] (Morton index of the cell), depth [K, 2]."""

@@ -257,10 +257,33 @@ class OctreeAS(BaseAS):
         return ASRaymarchResults(ridx=ridx, samples=samples, depth_samples=depth, deltas=deltas, boundary=boundary,
                                  ray_offsets=offsets)
 
-    def raymarch(self, rays, raymarch_type, num_samples, level=None) -> ASRaymarchResults:
+    def _raymarch_voxel_seeded(self, rays, num_samples, level, seed, step) -> ASRaymarchResults:
+        """`_raymarch_voxel` as the fused HIP march of render.raymarch_voxel: jitter restated from ``(seed, step)``, per-ray
+        pack offsets, and ``sample_capacity`` / ``last_sample_count`` honoured as `_raymarch_ray` does."""
+        from ... import render
+        level = self._level(level)
+        occ = self.occupancy_at(level, rays.origins.device)
+        capacity = getattr(self, "sample_capacity", None)
+        if capacity is not None:
+            ridx, samples, depth, deltas, boundary, offsets, self.last_sample_count = render.raymarch_voxel(
+                rays.origins, rays.dirs, occ, level, num_samples, seed, step, capacity=capacity)
+        else:
+            ridx, samples, depth, deltas, boundary, offsets = render.raymarch_voxel(
+                rays.origins, rays.dirs, occ, level, num_samples, seed, step)
+        return ASRaymarchResults(ridx=ridx, samples=samples, depth_samples=depth, deltas=deltas, boundary=boundary,
+                                 ray_offsets=offsets)
+
+    def raymarch(self, rays, raymarch_type, num_samples, level=None, seed=None, step=0) -> ASRaymarchResults:
+        """``seed`` (with 'voxel' only): the fused march whose jitter is a function of ``(seed, step, ray, nugget, sample)``
+        and which returns ``ray_offsets``; without it 'voxel' draws from torch's generator as the reference does. The 'ray'
+        marcher takes its randomness as a jitter tensor, so a seed is refused there."""
         if raymarch_type == "voxel":
+            if seed is not None:
+                return self._raymarch_voxel_seeded(rays, num_samples, level, seed, step)
             return self._raymarch_voxel(rays, num_samples, level)
         if raymarch_type == "ray":
+            if seed is not None:
+                raise ValueError("raymarch_type='ray' takes no seed: its jitter is a tensor (render.raymarch_ray)")
             return self._raymarch_ray(rays, num_samples, level)
         raise TypeError(f"Raymarch sampler type: {raymarch_type} is not supported by OctreeAS.")
 

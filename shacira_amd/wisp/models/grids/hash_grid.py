@@ -80,8 +80,9 @@ class _MultiLevelTable(BLASGrid):
             return feats.reshape(*output_shape, L, feats.shape[-1] // L).sum(-2)
         raise NotImplementedError
 
-    def raymarch(self, rays, raymarch_type, num_samples, level=None) -> ASRaymarchResults:
-        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=self.blas_level)
+    def raymarch(self, rays, raymarch_type, num_samples, level=None, seed=None, step=0) -> ASRaymarchResults:
+        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=self.blas_level, seed=seed,
+                                  step=step)
 
     def supported_blas(self) -> Set[Type[BaseAS]]:
         return {OctreeAS}

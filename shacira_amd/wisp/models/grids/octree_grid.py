@@ -166,9 +166,10 @@ class OctreeGrid(BLASGrid):
         feats = octree_ops.octree_interpolate(coords.reshape(-1, 3), lods, self._tables(num_feats), self.index, summed)
         return feats.reshape(*output_shape, feats.shape[-1])
 
-    def raymarch(self, rays, raymarch_type, num_samples, level=None) -> ASRaymarchResults:
+    def raymarch(self, rays, raymarch_type, num_samples, level=None, seed=None, step=0) -> ASRaymarchResults:
         """Samples over the coarsest level that has features, as the reference does."""
-        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=self.base_lod)
+        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=self.base_lod, seed=seed,
+                                  step=step)
 
     def raytrace(self, rays, level=None, with_exit=False) -> ASRaytraceResults:
         return self.blas.raytrace(rays, level=level, with_exit=with_exit)

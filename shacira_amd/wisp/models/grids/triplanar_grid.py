@@ -69,8 +69,9 @@ class TriplanarGrid(BLASGrid):
             return feats.reshape(*output_shape, feats.shape[-1])
         return feats.reshape(batch, num_samples, feats.shape[-1])
 
-    def raymarch(self, rays, raymarch_type, num_samples, level=None) -> ASRaymarchResults:
-        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=0)
+    def raymarch(self, rays, raymarch_type, num_samples, level=None, seed=None, step=0) -> ASRaymarchResults:
+        return self.blas.raymarch(rays, raymarch_type=raymarch_type, num_samples=num_samples, level=0, seed=seed,
+                                  step=step)
 
     def raytrace(self, rays, level=None, with_exit=False) -> ASRaytraceResults:
         return self.blas.raytrace(rays, level=0, with_exit=with_exit)

@@ -9,8 +9,12 @@ from ..core import RenderBuffer
 
 
 class PackedRFTracer:
-    def __init__(self, raymarch_type="voxel", num_steps=64, step_size=1.0, bg_color="white"):
+    def __init__(self, raymarch_type="voxel", num_steps=64, step_size=1.0, bg_color="white", seed=None):
+        """``seed`` (with ``raymarch_type="voxel"``): the fused seeded march (render.raymarch_voxel), whose per-ray offsets
+        take ``trace`` down its scatter-free branch. ``step`` tells the calls of one seed apart: a host counter incremented
+        per call, or a device int64 tensor its owner assigns and advances (a step replayed from a HIP graph)."""
         self.raymarch_type, self.num_steps, self.step_size, self.bg_color = raymarch_type, num_steps, step_size, bg_color
+        self.seed, self.step = seed, 0
 
     def get_supported_channels(self):
         return {"depth", "hit", "rgb", "alpha"}
@@ -35,8 +39,13 @@ class PackedRFTracer:
         if lod_idx is None:
             lod_idx = nef.grid.num_lods - 1
 
+        seeded = {}
+        if self.seed is not None and raymarch_type == "voxel":
+            seeded = dict(seed=self.seed, step=self.step)
+            if not torch.is_tensor(self.step):
+                self.step += 1
         marched = nef.grid.raymarch(rays, level=nef.grid.active_lods[lod_idx], num_samples=num_steps,
-                                    raymarch_type=raymarch_type)
+                                    raymarch_type=raymarch_type, **seeded)
         ridx, samples, deltas, boundary = marched.ridx, marched.samples, marched.deltas, marched.boundary
         num_samples = samples.shape[0]
         if num_samples == 0:
