@@ -46,7 +46,6 @@ const Options &opt() { return tl_options; }
 void options_snapshot() {
     for (OptionSlot &sl : g_slots) tl_options.*(sl.field) = sl.value.load(std::memory_order_relaxed);
 }
-void options_resolve_item12(int value) { tl_options.bwd_item12 = value; }
 static bool option_value_ok(const OptionSlot &sl, int v) {
     if (v < sl.lo || v > sl.hi) return false;
     if (!std::strcmp(sl.name, "fwd_variant")) return v == -1 || v == 0 || v == 3 || v == 6 || v == 8 || v == 9;
@@ -1010,14 +1009,12 @@ static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_
         else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
     }
     // a planned call is sized by what it runs: shacira_hashgrid_backward_planned_workspace_bytes when its brick pass takes the
-    // coarse levels (16-byte aligned grad_output), the plain size otherwise
-    const size_t need = plan != nullptr
-                            ? hashgrid_backward_workspace_planned(dim, dtype, lt, num_coords,
-                                                                  (reinterpret_cast<uintptr_t>(grad_output) & 15u) == 0)
-                            : hashgrid_backward_workspace(dim, dtype, lt, num_coords);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
-    return (int)hashgrid_backward_dispatch(dim, dtype, lt, codebook_first_idx, coords, grad_output, grad_codebook,
-                                           workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan);
+    // coarse levels (16-byte aligned grad_output), the plain size otherwise. The dispatcher checks it, before it launches
+    // anything, with the call it resolved for the launch.
+    bool too_small = false;
+    const hipError_t e = hashgrid_backward_dispatch(dim, dtype, lt, codebook_first_idx, coords, grad_output, grad_codebook,
+                                                    workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan, &too_small);
+    return too_small ? SHACIRA_EWORKSPACE : (int)e;
 }
 
 // ---- view shading ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 // Variant 0 ("atomic"): lane = (sample, level); per corner one global_atomic_add_f32 per feature. The
 //   accumulator is always fp32: for fp16 tables the sums are kept in an fp32 workspace and rounded once at the
 //   end (the reference rounds every __half2 atomicAdd, .cu:198-211; ours is the more accurate of the two).
+#include "bwd_bin_call.h"   // the binned form (hashgrid_bwd_bin.hip) and its resolved call
 #include "internal.h"
 
 namespace shacira {
@@ -252,16 +253,6 @@ static hipError_t bwd_atomic_f(const LevelTable &lt, const int32_t *first_idx, c
     return launch_bwd_atomic<DIM, T, 0>(lt, first_idx, coords, grad_out, acc, n, s);
 }
 
-// hashgrid_bwd_bin.hip
-bool bin_supported(int dim, const LevelTable &lt);
-bool bin_all_direct(int dim, const LevelTable &lt);
-size_t bin_workspace_bytes(int dim, int dtype, const LevelTable &lt, int64_t n);
-size_t bin_workspace_bytes_planned(int dim, int dtype, const LevelTable &lt, int64_t n, bool whole, bool grad_aligned);
-float *bin_acc32(int dim, int dtype, const LevelTable &lt, int64_t n, void *workspace);
-hipError_t bin_backward(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx, const float *coords,
-                        const void *grad_out, float *acc, void *workspace, int64_t n, hipStream_t s, bool zero_table,
-                        void *half_table, bool *converted, const SortedBatch *sb);
-
 // variant 1 ("bin") whenever the shape allows it and the batch is big enough to amortise its fixed passes
 static bool use_bin(int dim, const LevelTable &lt, int64_t n) {
     const int v = opt().bwd_variant;
@@ -280,40 +271,64 @@ static bool use_bin(int dim, const LevelTable &lt, int64_t n) {
     return n >= 4096;
 }
 
+// what a call needs beside the binned form's workspace: fp16 tables accumulate in an fp32 image
+static size_t acc32_bytes(int dtype, const LevelTable &lt) {
+    return dtype == SHACIRA_F16 ? (size_t)lt.table_rows * lt.feature_dim * sizeof(float) : 0;
+}
+
 size_t hashgrid_backward_workspace(int dim, int dtype, const LevelTable &lt, int64_t n) {
     if (dtype == SHACIRA_F64) return 0;   // atomicAdd(double) straight into the caller's table
-    size_t need = (dtype == SHACIRA_F16) ? (size_t)lt.table_rows * lt.feature_dim * sizeof(float) : 0;
+    size_t need = acc32_bytes(dtype, lt);
     if (bin_supported(dim, lt) && n > 0) {
-        const size_t b = bin_workspace_bytes(dim, dtype, lt, n);
+        BinCallBox box;
+        const size_t b = bin_workspace_bytes(bin_resolve(box, dim, dtype, lt, n, nullptr, false, false), lt);
         if (b > need) need = b;
     }
     return need;
 }
 
+// A planned call (a plan of the batch exists; level range = all levels, table zeroed by the call): the levels its brick pass
+// takes emit no items, the rest 12-byte units. A call the brick rule does not take is sized like the plain one.
 size_t hashgrid_backward_workspace_planned(int dim, int dtype, const LevelTable &lt, int64_t n, bool grad_aligned) {
-    if (dtype == SHACIRA_F64) return 0;
-    size_t need = (dtype == SHACIRA_F16) ? (size_t)lt.table_rows * lt.feature_dim * sizeof(float) : 0;
-    if (bin_supported(dim, lt) && n > 0) {
-        const bool whole = lt.level_begin == 0 && lt.level_end == lt.num_lods;
-        // (a batch below the binned form's threshold runs the atomic form: no items at all; sized like the plain query, which
-        // does not look at the threshold either)
-        const size_t b = (n < ((int64_t)1 << 31)) ? bin_workspace_bytes_planned(dim, dtype, lt, n, whole, grad_aligned)
-                                                  : bin_workspace_bytes(dim, dtype, lt, n);
-        if (b > need) need = b;
-    }
-    return need;
+    // (a batch below the binned form's threshold runs the atomic form: no items at all; sized like the plain query, which
+    // does not look at the threshold either)
+    if (dtype == SHACIRA_F64 || !bin_supported(dim, lt) || n <= 0 || n >= ((int64_t)1 << 31))
+        return hashgrid_backward_workspace(dim, dtype, lt, n);
+    SortedBatch sb{};
+    sample_plan_grid(dim, n, sb);
+    const bool whole = lt.level_begin == 0 && lt.level_end == lt.num_lods;
+    BinCallBox box;
+    const size_t need = acc32_bytes(dtype, lt), b = bin_workspace_bytes(bin_resolve(box, dim, dtype, lt, n, &sb, whole, grad_aligned), lt);
+    return b > need ? b : need;
 }
 
+// `too_small`: set (and nothing launched) when the call needs more than `workspace_bytes` -- the size the matching query returns
+// for it: the planned one with a plan at hand, the plain one otherwise. The binned form is resolved ONCE per call: the same
+// BinCall sizes the check, places the fp32 image and runs.
 hipError_t hashgrid_backward_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
                                       const float *coords, const void *grad_out, void *grad_table, void *workspace,
-                                      size_t workspace_bytes, int64_t n, hipStream_t s, const void *plan) {
-    (void)workspace_bytes;
+                                      size_t workspace_bytes, int64_t n, hipStream_t s, const void *plan, bool *too_small) {
+    *too_small = false;
     // the batch's plan (hashgrid_tiled.hip), when the caller kept the one its forward call built
     SortedBatch sbv{};
     const SortedBatch *sb = nullptr;
     if (plan != nullptr && n > 0 && n < ((int64_t)1 << 31)) {
         sample_plan_view(dim, n, plan, sbv);
         sb = &sbv;
+    }
+    const bool full = lt.level_begin == 0 && lt.level_end == lt.num_lods;
+    const bool binnable = dtype != SHACIRA_F64 && n > 0 && bin_supported(dim, lt);
+    BinCallBox box;
+    const BinCall *call = nullptr;
+    size_t need = dtype == SHACIRA_F64 ? 0 : acc32_bytes(dtype, lt);
+    if (binnable) {
+        call = &bin_resolve(box, dim, dtype, lt, n, sb, full, (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0);
+        const size_t b = bin_workspace_bytes(*call, lt);
+        if (b > need) need = b;
+    }
+    if (need > 0 && (!workspace || workspace_bytes < need)) {
+        *too_small = true;
+        return hipSuccess;
     }
     const int64_t numel = lt.table_rows * lt.feature_dim;
     if (dtype == SHACIRA_F64) {   // the reference-shaped form only: zeros_like, then one atomicAdd(double) per corner and feature
@@ -322,14 +337,13 @@ hipError_t hashgrid_backward_dispatch(int dim, int dtype, const LevelTable &lt, 
         return dim == 3 ? launch_bwd_atomic_f64<3>(lt, first_idx, coords, grad_out, grad_table, n, s)
                         : launch_bwd_atomic_f64<2>(lt, first_idx, coords, grad_out, grad_table, n, s);
     }
-    const bool bin = n > 0 && use_bin(dim, lt, n);
+    const bool bin = binnable && use_bin(dim, lt, n);
     // fp16 tables accumulate in an fp32 image: the tail of the bin workspace, or the whole workspace (atomic variant)
     float *acc = static_cast<float *>(grad_table);
     if (dtype == SHACIRA_F16) {
-        acc = bin ? bin_acc32(dim, dtype, lt, n, workspace) : static_cast<float *>(workspace);
+        acc = bin ? bin_acc32(*call, lt, workspace) : static_cast<float *>(workspace);
     }
     hipError_t e = hipSuccess;
-    const bool full = lt.level_begin == 0 && lt.level_end == lt.num_lods;
     if (full && bin) {
         // zeroed inside bin_backward (on its side stream, next to the transpose, when it forks)
     } else if (full) {
@@ -342,7 +356,7 @@ hipError_t hashgrid_backward_dispatch(int dim, int dtype, const LevelTable &lt, 
     if (e != hipSuccess) return e;
     bool converted = false;   // fp16 tables: the binned path may write the half table itself (single-unit buckets + a skipping conversion)
     if (bin) {
-        e = bin_backward(dim, dtype, lt, first_idx, coords, grad_out, acc, workspace, n, s, full,
+        e = bin_backward(*call, lt, first_idx, coords, grad_out, acc, workspace, s, full,
                          (dtype == SHACIRA_F16 && full) ? grad_table : nullptr, &converted, sb);
         if (e != hipSuccess) return e;
     } else if (n > 0) {

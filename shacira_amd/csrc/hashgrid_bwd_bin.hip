@@ -31,7 +31,14 @@
 //
 // Results differ from the reference only by summation order / two fp32 roundings per term (the reference's own
 // atomicAdd order is unspecified); tests hold them to 1e-5 relative against the fp64-accumulating oracle.
+//
+// Host side, in this order: the plans (make_plan: how a table's levels fall into buckets and direct groups), the workspace
+// layout (carve), the RESOLVER (bin_resolve: every per-call decision, once, into a BinCall -- the queries, the carving, the
+// plans and the launches read it), one launch function per kernel family (instantiation + LDS opt-in at first launch), and
+// run_bin, the launch sequence with its two forks onto the side stream.
 #include <mutex>
+#include <new>
+#include <type_traits>
 
 #include <cstring>
 
@@ -39,24 +46,38 @@
 #include "bwd_bin_front.h"
 #include "bwd_bin_passes.h"
 #include "bwd_brick.h"
+#include "bwd_bin_call.h"
 #include <hip/hip_ext.h>
 
 namespace shacira {
 
 // ------------------------------------------------------------------------------------------------- host side
+// One RESOLVED call (bwd_bin_call.h): host only, nothing here is a kernel argument. Filled by bin_resolve() alone.
+struct BinCall {
+    int dim, dtype;
+    int64_t n;                 // samples of the whole call
+    int acc_kib;               // LDS accumulator image per consumer workgroup (64 / 128)
+    bool one_image_compact;    // dense 3-D levels that fit ONE image travel as compact items, too
+    bool all_direct;           // every level of the TABLE fits an image, whatever level range the call names: nothing is staged
+    int fmt;                   // item stream: 0 = fp32 payloads (8 + 4 F bytes), 1 = half precision (fp16 tables), 2 = 12-byte units
+    size_t unit;               // bytes of one item unit in that format
+    int64_t nb;                // samples per sub-batch (the item array stays below option bin_batch_mib)
+    bool multi;                // nb < n
+    BrickPlan brick;           // the brick pass's levels (bwd_brick.h); nlev == 0: none
+    uint32_t skip_mask;        // ... as a level mask: neither binned nor direct in the item passes
+    uint32_t carve_skip;       // ... as the workspace LAYOUT sees it: fp16 tables keep the full layout (no levels skipped)
+};
+static_assert(sizeof(BinCall) <= sizeof(BinCallBox) && alignof(BinCall) <= alignof(BinCallBox) &&
+                  std::is_trivially_copyable<BinCall>::value && std::is_trivially_destructible<BinCall>::value,
+              "a BinCall lives in the dispatcher's BinCallBox");
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// `one_image_compact`: a dense 3-D level that fits ONE image travels as compact items too (one bucket whose units flush
-// atomically) instead of the direct pass in front of the scatter pass; decided per CALL from the total batch (below), so
-// that every plan of a call classifies the levels alike
+// The plan of `n_batch` samples (the whole call or one sub-batch) under the resolved call `c`: every plan of a call classifies
+// the levels alike (c.acc_kib, c.one_image_compact) and sizes its pad units and staging for the CALL's item format, not for the
+// one its own sample count would pick (round-5 advisor finding).
 // `skip_mask`: levels (bit l) another pass accumulates (the brick pass): neither binned nor direct here
-// `n_call`: samples of the whole CALL (0 = n_batch). The item format is chosen per call (run_bin, carve), so a sub-batch's plan
-// must size its pad units and staging for THAT format, not for the one its own sample count would pick (round-5 advisor finding)
-static void make_plan(int dim, int dtype, const LevelTable &lt, int64_t n_batch, BinPlan &plan, int acc_kib,
-                      bool one_image_compact, uint32_t skip_mask = 0u, int64_t n_call = 0);
-static inline bool half_items(int dtype, const LevelTable &lt);
-static inline int item_format(int dim, int dtype, const LevelTable &lt, int64_t n);
-static inline size_t item_unit_bytes(int fmt, const LevelTable &lt);
+static void make_plan(const BinCall &c, const LevelTable &lt, int64_t n_batch, BinPlan &plan, uint32_t skip_mask = 0u);
 #ifndef SHACIRA_RUN_ALIGN
 #define SHACIRA_RUN_ALIGN 64           // bytes a (tile, bucket) run is padded to: the memory system's write atom (measured:
                                        // runs on 64-byte boundaries stream at 4.7-5.0 TB/s, on 128-byte ones at 5.2-5.4, on
@@ -73,7 +94,31 @@ static inline size_t item_unit_bytes(int fmt, const LevelTable &lt);
                                        // samples, equal at 32 768, +2 % at 16 384: below, the hardware's own dispatch of the
                                        // ~1 400 tiny workgroups is as good)
 #endif
-static inline bool one_image_compact_rule(int64_t n_total) { return n_total >= ((int64_t)1 << 17); }
+
+// half-precision item stream: fp16 tables (bytes of one item unit: 8 + 4 F with fp32 payloads, 8 / 16 with half ones, or 12)
+static inline bool half_items(int dtype, const LevelTable &lt) {
+    return dtype == SHACIRA_F16 && (lt.feature_dim == 2 || lt.feature_dim == 4);
+}
+static inline size_t item_unit_bytes(int fmt, const LevelTable &lt) {
+    if (fmt == 1) return lt.feature_dim == 2 ? 8 : 16;
+    if (fmt == 2) return 12;
+    return 8 + 4 * (size_t)lt.feature_dim;
+}
+
+// A call that only asks how a table's levels fall into buckets and groups under (acc_kib, one_image_compact): one tile of
+// samples, the table's base item format (at that size no plan pads its runs, so the format does not show).
+static BinCall probe_call(int dim, int dtype, const LevelTable &lt, int acc_kib, bool one_image_compact) {
+    BinCall c{};
+    c.dim = dim;
+    c.dtype = dtype;
+    c.n = kTile;
+    c.acc_kib = acc_kib;
+    c.one_image_compact = one_image_compact;
+    c.fmt = half_items(dtype, lt) ? 1 : 0;
+    c.unit = item_unit_bytes(c.fmt, lt);
+    c.nb = kTile;
+    return c;
+}
 
 // can the table be partitioned with an LDS accumulator image of `acc_kib` KiB per consumer workgroup?
 static bool bin_feasible(int dim, int dtype, const LevelTable &lt, int acc_kib) {
@@ -92,7 +137,7 @@ static bool bin_feasible(int dim, int dtype, const LevelTable &lt, int acc_kib) 
         }
     }
     BinPlan plan;
-    make_plan(dim, dtype, lt, kTile, plan, acc_kib, false);
+    make_plan(probe_call(dim, dtype, lt, acc_kib, false), lt, kTile, plan);
     if (plan.total_buckets + (uint32_t)lt.num_lods > (uint32_t)kMaxBuckets) return false;   // (+ one-image compact levels)
     for (int l = 0; l < lt.num_lods; ++l)
         if (plan.lv[l].nb > (uint32_t)kMaxLevelBuckets) return false;
@@ -115,17 +160,15 @@ static int choose_acc_kib(int dim, int dtype, const LevelTable &lt, int64_t n) {
     // tables whose levels are all "direct" (config B: every level fits an LDS image) want the big image: fewer level
     // groups, hence fewer walks over the samples (measured 82 vs 124 us on the 393 216-pixel batch)
     BinPlan big;
-    make_plan(dim, dtype, lt, kTile, big, 128, false);
+    make_plan(probe_call(dim, dtype, lt, 128, false), lt, kTile, big);
     return big.nbl == 0 ? 128 : 64;
 }
-
-bool bin_supported(int dim, const LevelTable &lt);
 
 // every level fits an LDS image (no level is binned): the backward is the direct-level kernel alone
 bool bin_all_direct(int dim, const LevelTable &lt) {
     if (!bin_supported(dim, lt)) return false;
     BinPlan plan;
-    make_plan(dim, SHACIRA_F32, lt, kTile, plan, 128, false);
+    make_plan(probe_call(dim, SHACIRA_F32, lt, 128, false), lt, kTile, plan);
     return plan.nbl == 0 && plan.ngroups > 0;
 }
 
@@ -135,20 +178,18 @@ bool bin_supported(int dim, const LevelTable &lt) {
     return bin_feasible(dim, SHACIRA_F32, lt, kib ? kib : 128);
 }
 
-static void make_plan_uncached(int dim, int dtype, const LevelTable &lt, int64_t n_batch, BinPlan &plan, int acc_kib,
-                               bool one_image_compact, uint32_t skip_mask, int64_t n_call);
+static void make_plan_uncached(const BinCall &c, const LevelTable &lt, int64_t n_batch, BinPlan &plan, bool one_image_compact,
+                               uint32_t skip_mask);
 
-// A backward call plans several times (workspace query, carving, image-size rule, the run itself), and a plan costs a few
-// microseconds of host time (the magic-division checks of the compact levels walk every line): small batches became
-// HOST-bound (2-D bw-19 table at 2^17 samples: 0.123 ms per call against 0.094 ms of GPU time). Plans are pure functions of
-// their arguments and two options, so each thread keeps its last few.
-static void make_plan(int dim, int dtype, const LevelTable &lt, int64_t n_batch, BinPlan &plan, int acc_kib,
-                      bool one_image_compact, uint32_t skip_mask, int64_t n_call) {
-    if (n_call <= 0) n_call = n_batch;
+// A backward call plans several times (the image-size rule, the brick rule, the carving, the run and its sub-batches), and a
+// plan costs a few microseconds of host time (the magic-division checks of the compact levels walk every line): small batches
+// became HOST-bound (2-D bw-19 table at 2^17 samples: 0.123 ms per call against 0.094 ms of GPU time). Plans are pure functions
+// of their arguments, the call's decisions and two options, so each thread keeps its last few.
+static void make_plan(const BinCall &c, const LevelTable &lt, int64_t n_batch, BinPlan &plan, uint32_t skip_mask) {
     struct Key {
-        int dim, dtype, acc_kib, oic, compact, run_pad, item12, fmt;
+        int dim, dtype, acc_kib, oic, compact, run_pad, fmt;
         uint32_t skip_mask;
-        int64_t n_batch;
+        int64_t n_batch, n_call;
         LevelTable lt;
     };
     struct Entry {
@@ -161,12 +202,12 @@ static void make_plan(int dim, int dtype, const LevelTable &lt, int64_t n_batch,
     thread_local int next = 0;
     Key k;
     std::memset(&k, 0, sizeof(k));     // (padding bytes take part in the comparison)
-    k.dim = dim; k.dtype = dtype; k.acc_kib = acc_kib; k.oic = one_image_compact ? 1 : 0; k.compact = opt().bwd_compact;
+    k.dim = c.dim; k.dtype = c.dtype; k.acc_kib = c.acc_kib; k.oic = c.one_image_compact ? 1 : 0; k.compact = opt().bwd_compact;
     k.run_pad = opt().bwd_run_pad;
-    k.item12 = opt().bwd_item12;
+    k.fmt = c.fmt;
     k.skip_mask = skip_mask;
-    k.fmt = item_format(dim, dtype, lt, n_call);
     k.n_batch = n_batch;
+    k.n_call = c.n;
     std::memcpy(&k.lt, &lt, sizeof(LevelTable));
     for (int e = 0; e < kEntries; ++e) {
         if (cache[e].valid && std::memcmp(&cache[e].key, &k, sizeof(Key)) == 0) {
@@ -174,7 +215,7 @@ static void make_plan(int dim, int dtype, const LevelTable &lt, int64_t n_batch,
             return;
         }
     }
-    make_plan_uncached(dim, dtype, lt, n_batch, plan, acc_kib, one_image_compact, skip_mask, n_call);
+    make_plan_uncached(c, lt, n_batch, plan, c.one_image_compact, skip_mask);
     Entry &slot = cache[next];
     next = (next + 1) % kEntries;
     slot.key = k;
@@ -182,12 +223,14 @@ static void make_plan(int dim, int dtype, const LevelTable &lt, int64_t n_batch,
     slot.valid = true;
 }
 
-static void make_plan_uncached(int dim, int dtype, const LevelTable &lt, int64_t n_batch, BinPlan &plan, int acc_kib,
-                               bool one_image_compact, uint32_t skip_mask, int64_t n_call) {
+static void make_plan_uncached(const BinCall &c, const LevelTable &lt, int64_t n_batch, BinPlan &plan, bool one_image_compact,
+                               uint32_t skip_mask) {
     if (one_image_compact) {   // tables whose levels are ALL direct stay that way (no transposing pass at all)
-        make_plan_uncached(dim, dtype, lt, n_batch, plan, acc_kib, false, skip_mask, n_call);
+        make_plan_uncached(c, lt, n_batch, plan, false, skip_mask);
         if (plan.nbl == 0) return;
     }
+    const int dim = c.dim, dtype = c.dtype, acc_kib = c.acc_kib;
+    const int64_t n_call = c.n;
     const int F = lt.feature_dim;
     const uint32_t BR = (uint32_t)acc_kib * 128u / (uint32_t)F;
     uint32_t shift = 0;
@@ -334,8 +377,8 @@ static void make_plan_uncached(int dim, int dtype, const LevelTable &lt, int64_t
     // pad slots staged.
     plan.pad = 1;
     {
-        const int fmt_p = item_format(dim, dtype, lt, n_call);   // the CALL's format (see the declaration)
-        const size_t unit = item_unit_bytes(fmt_p, lt);
+        const int fmt_p = c.fmt;   // the CALL's format (see the declaration)
+        const size_t unit = c.unit;
         const uint32_t tile_units = (uint32_t)tile_samples(dim) * plan.pairs;
         uint32_t maxnb = 0;
         for (uint32_t q = 0; q < plan.nbl; ++q) maxnb = plan.lv[plan.blevel[q]].nb > maxnb ? plan.lv[plan.blevel[q]].nb : maxnb;
@@ -379,37 +422,6 @@ static void make_plan_uncached(int dim, int dtype, const LevelTable &lt, int64_t
     plan.chunk_min = plan.chunk;
 }
 
-// sub-batch so that the item array stays below the cap (default 1.5 GiB, option "bin_batch_mib")
-// bytes of one item unit: 8 + 4 F (fp32 payloads), 8 with the half-precision stream (fp16 tables, F = 2)
-static inline bool half_items(int dtype, const LevelTable &lt) {
-    return dtype == SHACIRA_F16 && (lt.feature_dim == 2 || lt.feature_dim == 4);
-}
-// item stream format of a call: 0 = fp32 payloads (8 + 4 F bytes per unit), 1 = half-precision stream (fp16 tables), 2 = 12-byte
-// units (fp32 tables, 3-D, F = 2, batches that accumulate in fixed-point images; option "bwd_item12")
-static inline int item_format(int dim, int dtype, const LevelTable &lt, int64_t n) {
-    if (half_items(dtype, lt)) return 1;
-    // (bwd_item12 = -1, the automatic setting, is resolved per call by bin_backward before anything is sized; a workspace query
-    // sees -1 and sizes for the 16-byte stream, the larger of the two)
-    if (dim == 3 && lt.feature_dim == 2 && dtype == SHACIRA_F32 && n >= SHACIRA_FX_MIN && opt().bwd_item12 == 1) return 2;
-    return 0;
-}
-static inline size_t item_unit_bytes(int fmt, const LevelTable &lt) {
-    if (fmt == 1) return lt.feature_dim == 2 ? 8 : 16;
-    if (fmt == 2) return 12;
-    return 8 + 4 * (size_t)lt.feature_dim;
-}
-
-static int64_t bin_batch_samples(int dim, int dtype, const LevelTable &lt, int64_t n) {
-    const size_t item = item_unit_bytes(item_format(dim, dtype, lt, n), lt);
-    BinPlan plan;
-    make_plan(dim, dtype, lt, kTile, plan, choose_acc_kib(dim, dtype, lt, n), one_image_compact_rule(n));
-    const size_t per_sample = (size_t)(plan.nbl ? plan.nbl : 1) * (1u << (dim - 1)) * item;
-    int64_t cap = (int64_t)(((size_t)opt().bin_batch_mib << 20) / per_sample);
-    cap = cap / tile_samples(dim) * tile_samples(dim);
-    if (cap < tile_samples(dim)) cap = tile_samples(dim);
-    return n < cap ? n : cap;
-}
-
 struct BinWorkspace {
     float *gT;                    // [L][NP][F] transposed gradients, NP = n rounded up to even
     unsigned char *items;
@@ -427,17 +439,6 @@ struct BinWorkspace {
 
 static inline int64_t level_pitch(int64_t n) { return (n + 1) & ~(int64_t)1; }
 
-// every level of the table is "direct" (fits an LDS image) whatever level range a call names: such tables never need the
-// transposed gradients nor items (the image configs B / C / kodak.yaml: the direct kernel reads grad_output itself)
-static bool table_all_direct(int dim, int dtype, const LevelTable &lt, int64_t n) {
-    LevelTable full = lt;
-    full.level_begin = 0;
-    full.level_end = lt.num_lods;
-    BinPlan plan;
-    make_plan(dim, dtype, full, kTile, plan, choose_acc_kib(dim, dtype, full, n), one_image_compact_rule(n));
-    return plan.nbl == 0;
-}
-
 // 16-byte (item-unit) slots one sample can occupy over all binned levels of the plan: x-pair items 2^(dim-1) per level,
 // compact 3-D levels two slots, compact 2-D levels one
 static uint64_t slots_per_sample(const BinPlan &plan) {
@@ -451,61 +452,20 @@ static uint64_t slots_per_sample(const BinPlan &plan) {
 
 static int front_tile(int L, int F, uint32_t nbl, int64_t n, size_t *shmem);
 
-// The brick pass's levels for a call (bwd_brick.h), or none: with the batch's plan at hand (the cell-sorted forward's records;
-// only its block grid `sb->nb` is read here), coarse 3-D levels are accumulated block by block in LDS and leave the item stream.
-// Whole calls over one sub-batch that accumulate in fixed point (>= 2^17 samples: the regime the item stream binds in); never for
-// tables whose levels are all direct. One function for the workspace query, the carving and the launch sequence.
-// Measured rule (option bwd_brick = -1; tools/brick_cfg_ab.py, profiles/r06_experiments.md 3 + 7): fp32 item streams of
-// F = 2 tables, at every batch size that has a plan (the forward sorts from 2^18 samples) -- with the 12-byte item units
-// the pass brings along, S1 backward at 2^20 / 2^19 / 2^18 samples: 0.468 -> 0.417 / 0.270 -> 0.252 / 0.166 -> 0.161 ms.
-// Not taken: half-precision item streams (items are half the bytes already: S1 fp16 0.415 -> 0.435) and F = 4
-// (nerf_lego.yaml's table: 32 LDS atomics per sample and level, six of its eleven dense levels do not fit the images
-// and would stay compact items in sorted order: 0.612 -> 0.617, fp16 0.504 -> 0.508). bwd_brick = 1 takes it wherever
-// the shape allows.
-static void brick_levels_of_call(int dim, int dtype, const LevelTable &lt, int64_t n, const SortedBatch *sb, bool zero_table,
-                                 bool grad_aligned, BrickPlan &brick, uint32_t &skip_mask) {
-    brick.nlev = 0;
-    skip_mask = 0u;
-    if (dim != 3 || sb == nullptr) return;
-    const int L = lt.num_lods, F = lt.feature_dim;
-    const bool multi = bin_batch_samples(dim, dtype, lt, n) < n;
-    // (sorted mode rides on the fused 16-byte front kernel: rows of whole 16-byte vectors, 16-byte aligned input)
-    const int kvec0 = (int)(16 / ((dtype == SHACIRA_F32 ? 4 : 2) * F));
-    const int bopt = opt().bwd_brick;
-    const bool wanted = bopt == 1 || (bopt < 0 && F == 2 && dtype == SHACIRA_F32);
-    if (!wanted || multi || lt.stage_flags != 0 || !zero_table || n < SHACIRA_FX_MIN || n * L >= ((int64_t)1 << 31) ||
-        table_all_direct(dim, dtype, lt, n) || (L % kvec0) != 0 || !grad_aligned)
-        return;
-    // beside the consume pass (mode 2) a brick workgroup must fit the LDS its 128 KiB image leaves
-    if (!make_brick_plan(lt, n, *sb, opt().bwd_brick_lo, opt().bwd_brick_hi, opt().bwd_brick_span,
-                         (size_t)(opt().bwd_brick_fork == 2 ? 30 : 64) * 1024, brick)) {
-        brick.nlev = 0;
-        return;
-    }
-    for (uint32_t q = 0; q < brick.nlev; ++q) skip_mask |= 1u << brick.lv[q].level;
-    // (nothing left for the item passes, or no tile size for the fused front kernel: keep the plain pipeline)
-    BinPlan rest;
-    make_plan(dim, dtype, lt, n, rest, choose_acc_kib(dim, dtype, lt, n), one_image_compact_rule(n), skip_mask, n);
-    size_t sh0 = 0;
-    if (rest.nbl == 0 || front_tile(L, F, rest.nbl, n, &sh0) <= 0) {
-        skip_mask = 0u;
-        brick.nlev = 0;
-    }
-}
-
-// skip_mask: the levels the call's brick pass takes (brick_levels_of_call): they emit no items
-static BinWorkspace carve(int dim, int dtype, const LevelTable &lt, int64_t n, void *ws, uint32_t skip_mask = 0u) {
+// The workspace of a resolved call (ws == NULL: its size only)
+static BinWorkspace carve(const BinCall &c, const LevelTable &lt, void *ws) {
+    const int dtype = c.dtype;
+    const int64_t n = c.n, nb = c.nb;
+    const size_t item = c.unit;
     BinPlan plan;
-    const int64_t nb = bin_batch_samples(dim, dtype, lt, n);
-    make_plan(dim, dtype, lt, nb, plan, choose_acc_kib(dim, dtype, lt, n), one_image_compact_rule(n), skip_mask, n);
-    const size_t item = item_unit_bytes(item_format(dim, dtype, lt, n), lt);
+    make_plan(c, lt, nb, plan, c.carve_skip);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     // gT and gmax first: their offsets must not depend on the level range of the call (REUSE_STAGED calls share them).
     // Sized by what the selected path uses (round 4): an all-direct table stages nothing -- config C's query returned 1.21 GB
     // for a call that ran one kernel on grad_output -- and the item array holds the slots the plan's levels can emit
     // (compact levels: 2 of the 4 pair slots), S1: 1.23 -> 1.05 GB.
-    const bool no_stage = table_all_direct(dim, dtype, lt, n);
+    const bool no_stage = c.all_direct;
     const size_t o_gT = take(no_stage ? 0 : (size_t)level_pitch(n) * lt.num_lods * lt.feature_dim * sizeof(float));
     const size_t o_ctrl = take((size_t)(kTotalShards * kMaxBuckets + SHACIRA_MAX_LODS) * sizeof(uint32_t));   // totals | gmax: one memset
     // (+ the pad units of line-aligned runs: at most pad - 1 per (scatter tile, bucket))
@@ -536,45 +496,103 @@ static BinWorkspace carve(int dim, int dtype, const LevelTable &lt, int64_t n, v
     return w;
 }
 
-// Item format and brick levels of one call (the thread's option snapshot of this C-ABI call is updated in place).
-// 12-byte item units, automatic setting: with the brick pass, i.e. on planned calls of the shapes its rule takes. In sorted order
-// with the dense levels out of the item stream the consume pass has the instruction slots the unpacking costs (S1 backward
-// 0.440 -> 0.417 ms; on the plain path the format returns 1-3 %; profiles/r06_experiments.md 7). Decided before the workspace is
-// sized or carved: every plan and pass of the call then sees one format.
-static void resolve_call(int dim, int dtype, const LevelTable &lt, int64_t n, const SortedBatch *sb, bool zero_table,
-                         bool grad_aligned, BrickPlan &brick, uint32_t &skip_mask) {
-    const bool auto12 = opt().bwd_item12 < 0;
-    if (auto12) {
-        const bool brick_shape = sb != nullptr && dim == 3 && lt.feature_dim == 2 && dtype == SHACIRA_F32 &&
-                                 lt.level_begin == 0 && lt.level_end == lt.num_lods && lt.stage_flags == 0 && zero_table &&
-                                 opt().bwd_brick != 0;
-        options_resolve_item12(brick_shape ? 1 : 0);
+// ---- the resolver: everything the binned backward decides per call, decided once ---------------------------------------------
+
+// The item format `fmt` and what follows from it: the sub-batch size that keeps the item array below the cap (default
+// 1.5 GiB, option "bin_batch_mib")
+static void set_item_format(BinCall &c, const LevelTable &lt, int fmt) {
+    c.fmt = fmt;
+    c.unit = item_unit_bytes(fmt, lt);
+    BinPlan plan;
+    make_plan(probe_call(c.dim, c.dtype, lt, c.acc_kib, c.one_image_compact), lt, kTile, plan);
+    const size_t per_sample = (size_t)(plan.nbl ? plan.nbl : 1) * (1u << (c.dim - 1)) * c.unit;
+    int64_t cap = (int64_t)(((size_t)opt().bin_batch_mib << 20) / per_sample);
+    cap = cap / tile_samples(c.dim) * tile_samples(c.dim);
+    if (cap < tile_samples(c.dim)) cap = tile_samples(c.dim);
+    c.nb = c.n < cap ? c.n : cap;
+    c.multi = c.nb < c.n;
+}
+
+// The brick pass's levels for a call (bwd_brick.h), or none: with the batch's plan at hand (the cell-sorted forward's records;
+// only its block grid `sb->nb` is read here), coarse 3-D levels are accumulated block by block in LDS and leave the item stream.
+// Whole calls over one sub-batch that accumulate in fixed point (>= 2^17 samples: the regime the item stream binds in); never for
+// tables whose levels are all direct. Sees the call as resolved so far (its tentative item format included) and fills c.brick / c.skip_mask.
+// Measured rule (option bwd_brick = -1; tools/brick_cfg_ab.py, profiles/r06_experiments.md 3 + 7): fp32 item streams of
+// F = 2 tables, at every batch size that has a plan (the forward sorts from 2^18 samples) -- with the 12-byte item units
+// the pass brings along, S1 backward at 2^20 / 2^19 / 2^18 samples: 0.468 -> 0.417 / 0.270 -> 0.252 / 0.166 -> 0.161 ms.
+// Not taken: half-precision item streams (items are half the bytes already: S1 fp16 0.415 -> 0.435) and F = 4
+// (nerf_lego.yaml's table: 32 LDS atomics per sample and level, six of its eleven dense levels do not fit the images
+// and would stay compact items in sorted order: 0.612 -> 0.617, fp16 0.504 -> 0.508). bwd_brick = 1 takes it wherever
+// the shape allows.
+static void resolve_brick(BinCall &c, const LevelTable &lt, const SortedBatch *sb, bool zero_table, bool grad_aligned) {
+    BrickPlan &brick = c.brick;
+    brick.nlev = 0;
+    c.skip_mask = 0u;
+    const int dim = c.dim, dtype = c.dtype;
+    const int64_t n = c.n;
+    if (dim != 3 || sb == nullptr) return;
+    const int L = lt.num_lods, F = lt.feature_dim;
+    // (sorted mode rides on the fused 16-byte front kernel: rows of whole 16-byte vectors, 16-byte aligned input)
+    const int kvec0 = (int)(16 / ((dtype == SHACIRA_F32 ? 4 : 2) * F));
+    const int bopt = opt().bwd_brick;
+    const bool wanted = bopt == 1 || (bopt < 0 && F == 2 && dtype == SHACIRA_F32);
+    if (!wanted || c.multi || lt.stage_flags != 0 || !zero_table || n < SHACIRA_FX_MIN || n * L >= ((int64_t)1 << 31) ||
+        c.all_direct || (L % kvec0) != 0 || !grad_aligned)
+        return;
+    // beside the consume pass (mode 2) a brick workgroup must fit the LDS its 128 KiB image leaves
+    if (!make_brick_plan(lt, n, *sb, opt().bwd_brick_lo, opt().bwd_brick_hi, opt().bwd_brick_span,
+                         (size_t)(opt().bwd_brick_fork == 2 ? 30 : 64) * 1024, brick)) {
+        brick.nlev = 0;
+        return;
     }
-    brick_levels_of_call(dim, dtype, lt, n, sb, zero_table, grad_aligned, brick, skip_mask);
-    if (auto12 && brick.nlev == 0) options_resolve_item12(0);
-}
-// (fp16 tables keep the full layout: the offset of their fp32 accumulation image is asked for before the call is resolved)
-static inline uint32_t carve_skip(int dtype, uint32_t skip_mask) { return dtype == SHACIRA_F32 ? skip_mask : 0u; }
-
-size_t bin_workspace_bytes(int dim, int dtype, const LevelTable &lt, int64_t n) {
-    return carve(dim, dtype, lt, n, nullptr).bytes;
-}
-
-// workspace of a PLANNED call (a plan of the batch exists; `whole`: level range = all levels, table zeroed by the call;
-// `grad_aligned`: 16-byte aligned grad_output): the levels its brick pass takes emit no items, the rest 12-byte units. A call
-// the brick rule does not take is sized like the plain one.
-size_t bin_workspace_bytes_planned(int dim, int dtype, const LevelTable &lt, int64_t n, bool whole, bool grad_aligned) {
-    SortedBatch sb{};
-    sample_plan_grid(dim, n, sb);
-    BrickPlan brick;
-    uint32_t skip_mask = 0;
-    resolve_call(dim, dtype, lt, n, &sb, whole, grad_aligned, brick, skip_mask);
-    return carve(dim, dtype, lt, n, nullptr, carve_skip(dtype, skip_mask)).bytes;
+    uint32_t skip_mask = 0u;
+    for (uint32_t q = 0; q < brick.nlev; ++q) skip_mask |= 1u << brick.lv[q].level;
+    // (nothing left for the item passes, or no tile size for the fused front kernel: keep the plain pipeline)
+    BinPlan rest;
+    make_plan(c, lt, n, rest, skip_mask);
+    size_t sh0 = 0;
+    if (rest.nbl == 0 || front_tile(L, F, rest.nbl, n, &sh0) <= 0) brick.nlev = 0;
+    else c.skip_mask = skip_mask;
 }
 
-float *bin_acc32(int dim, int dtype, const LevelTable &lt, int64_t n, void *workspace) {
-    return carve(dim, dtype, lt, n, workspace).acc32;
+// One call, resolved. The only reader of option "bwd_item12" (-1 / 0 / 1, the user's setting for the whole call).
+// 12-byte item units (fp32 tables, 3-D, F = 2, batches that accumulate in fixed-point images), automatic setting: with the brick
+// pass, i.e. on planned calls of the shapes its rule takes. In sorted order with the dense levels out of the item stream the
+// consume pass has the instruction slots the unpacking costs (S1 backward 0.440 -> 0.417 ms; on the plain path the format returns
+// 1-3 %; profiles/r06_experiments.md 7). Two steps, in this order: the 12-byte format is assumed while the brick rule is
+// evaluated (its sub-batch test sees that format), and falls back to the 16-byte stream if the rule declines. A call without a
+// plan (every plain workspace query) therefore sizes for the 16-byte stream, the larger of the two.
+const BinCall &bin_resolve(BinCallBox &box, int dim, int dtype, const LevelTable &lt, int64_t n, const SortedBatch *sb,
+                           bool zero_table, bool grad_aligned) {
+    BinCall &c = *new (box.raw) BinCall{};
+    c.dim = dim;
+    c.dtype = dtype;
+    c.n = n;
+    c.acc_kib = choose_acc_kib(dim, dtype, lt, n);
+    c.one_image_compact = n >= ((int64_t)1 << 17);
+    {   // (the image configs B / C / kodak.yaml: the direct kernel reads grad_output itself, no transposed gradients nor items)
+        LevelTable full = lt;
+        full.level_begin = 0;
+        full.level_end = lt.num_lods;
+        BinPlan plan;
+        make_plan(probe_call(dim, dtype, full, choose_acc_kib(dim, dtype, full, n), c.one_image_compact), full, kTile, plan);
+        c.all_direct = plan.nbl == 0;
+    }
+    const int item12 = opt().bwd_item12;
+    const bool fits12 = dim == 3 && lt.feature_dim == 2 && dtype == SHACIRA_F32 && n >= SHACIRA_FX_MIN;
+    const bool brick_shape = sb != nullptr && dim == 3 && lt.feature_dim == 2 && dtype == SHACIRA_F32 && lt.level_begin == 0 &&
+                             lt.level_end == lt.num_lods && lt.stage_flags == 0 && zero_table && opt().bwd_brick != 0;
+    const int base = half_items(dtype, lt) ? 1 : 0;
+    set_item_format(c, lt, (base == 0 && fits12 && (item12 == 1 || (item12 < 0 && brick_shape))) ? 2 : base);
+    resolve_brick(c, lt, sb, zero_table, grad_aligned);
+    if (item12 < 0 && c.brick.nlev == 0 && c.fmt == 2) set_item_format(c, lt, base);
+    c.carve_skip = dtype == SHACIRA_F32 ? c.skip_mask : 0u;
+    return c;
 }
+
+size_t bin_workspace_bytes(const BinCall &call, const LevelTable &lt) { return carve(call, lt, nullptr).bytes; }
+
+float *bin_acc32(const BinCall &call, const LevelTable &lt, void *workspace) { return carve(call, lt, workspace).acc32; }
 
 #define SHACIRA_CHECK_LAUNCH()                 \
     do {                                       \
@@ -645,31 +663,267 @@ static int front_tile(int L, int F, uint32_t nbl, int64_t n, size_t *shmem) {
     }
 }
 
+// Joins a side stream back into the caller's stream on EVERY way out of run_bin. Once the side stream waits on the caller's
+// stream (fork), an early error return still records the join event on it and makes the caller's stream wait for it: the side
+// stream may be reading the caller's workspace, and a stream capture must not be left with an unjoined branch. The success path
+// records and waits where it always did (those positions were measured) and the guard then has nothing left to do.
+struct SideJoin {
+    hipStream_t main, side = nullptr;   // side != nullptr: forked
+    hipEvent_t join = nullptr;
+    bool recorded = false, waited = false;
+    explicit SideJoin(hipStream_t m) : main(m) {}
+    SideJoin(const SideJoin &) = delete;
+    SideJoin &operator=(const SideJoin &) = delete;
+    // `fork_signalled`: a launch on the caller's stream signals fork_ev itself (hipExtLaunchKernelGGL's stop event)
+    hipError_t fork(hipStream_t side_, hipEvent_t fork_ev, hipEvent_t join_ev, bool fork_signalled = false) {
+        if (!fork_signalled) SHACIRA_CHECK(hipEventRecord(fork_ev, main));
+        SHACIRA_CHECK(hipStreamWaitEvent(side_, fork_ev, 0));
+        side = side_;
+        join = join_ev;
+        return hipSuccess;
+    }
+    hipError_t record() {
+        const hipError_t e = hipEventRecord(join, side);
+        recorded = e == hipSuccess;
+        return e;
+    }
+    void signalled() { recorded = true; }   // a launch on the side stream signals the join event itself
+    hipError_t wait() {
+        const hipError_t e = hipStreamWaitEvent(main, join, 0);
+        waited = e == hipSuccess;
+        return e;
+    }
+    ~SideJoin() {
+        if (side == nullptr || waited) return;
+        if (!recorded) (void)hipEventRecord(join, side);
+        (void)hipStreamWaitEvent(main, join, 0);
+    }
+};
+
+// ---- launches: one function per kernel family. It selects the instantiation and, at an instantiation's first launch on a
+// device, opts it in for more than 64 KiB of dynamic LDS (hipFuncSetAttribute is a per-device setting and no stream operation;
+// the PerDeviceOnce idiom of hashgrid_fwd.hip) -- an instantiation that is launched is opted in, there is no list to keep.
+template <auto Kernel> struct KernelTag { static constexpr auto value = Kernel; };
+
+// `cap`: the most dynamic LDS any launch asks of the instantiation (its static LDS comes on top and must fit in 160 KiB too).
+// 64 KiB or less needs no opt-in; beyond the CU's LDS a launch fails by itself.
+template <auto Kernel> static hipError_t lds_opt_in(size_t cap) {
+    if (cap <= 64 * 1024 || cap > 160 * 1024) return hipSuccess;
+    static PerDeviceOnce once;
+    return once.run([cap]() -> hipError_t {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+    });
+}
+// (launched through its address a kernel has no default arguments: every launch names them all)
+template <auto Kernel, class... Args>
+static hipError_t launch_lds(size_t cap, dim3 grid, dim3 block, size_t shmem, hipStream_t s, Args... args) {
+    SHACIRA_CHECK(lds_opt_in<Kernel>(cap));
+    hipLaunchKernelGGL(Kernel, grid, block, shmem, s, args...);
+    return hipGetLastError();
+}
+
+// what the passes of one call share
+struct BinRun {
+    const LevelTable &lt;
+    const BinWorkspace &w;
+    const int32_t *first_idx;
+    const float *coords;      // the caller's [n, DIM]
+    const void *grad_out;
+    float *acc;
+    int dtype;
+    int64_t n, NP;            // samples, pitch of a level of gT
+    bool use_fx;              // fixed-point images (and the gmax bookkeeping)
+    const float *cptr;        // coordinates as the passes behind the front pass walk them: the caller's, or (SORTED mode) the
+    int cstride;              // plan's records {x, y, z, sample index}; floats per record
+    const SortedBatch *sb;
+};
+
+// pass F / pass T: grad_output -> gT (levels [t_lb, t_le)), fused with the bucket counting (`counts`) and the per-level
+// max |gradient| (r.use_fx). `ts16` > 0: the 16-byte front kernel on tiles of that many samples; 0: the 8-byte transpose
+template <int DIM, typename T, int F>
+static hipError_t launch_front_as(const BinRun &r, const BinPlan &whole, int ts16, size_t front_shmem, bool counts, bool sorted,
+                                  int t_lb, int t_le, hipStream_t s) {
+    const T *go = static_cast<const T *>(r.grad_out);
+    if (ts16 <= 0) {
+        const int L = r.lt.num_lods;
+        const uint32_t blocks = (uint32_t)((r.n + 255) / 256);
+        const size_t shmem = (size_t)256 * (L + 1) * F * sizeof(float);
+        const auto launch = [&](auto k, uint32_t *gmax) -> hipError_t {
+            return launch_lds<decltype(k)::value>(140 * 1024, dim3(blocks), dim3(256), shmem, s, go, r.w.gT, r.n, r.NP, L, t_lb,
+                                                  t_le, gmax);
+        };
+        return r.use_fx ? launch(KernelTag<&transpose_grad_kernel<T, F, true>>{}, r.w.gmax)
+                        : launch(KernelTag<&transpose_grad_kernel<T, F, false>>{}, nullptr);
+    }
+    // ~512 workgroups (two per CU, all resident) when the batch allows; never fewer than one tile per workgroup
+    const int64_t tiles = (r.n + ts16 - 1) / ts16;
+    int ts_log2 = 7;
+    while ((1 << ts_log2) < ts16) ++ts_log2;
+    int rounds = (int)((tiles + 511) / 512);
+    // padded runs: a workgroup's counting tiles must be whole scatter tiles (the pad units are per scatter tile)
+    const int cps16 = TileOf<DIM>::value / ts16;
+    if (whole.pad > 1u && counts) rounds = (rounds + cps16 - 1) / cps16 * cps16;
+    const uint32_t blocks = (uint32_t)((tiles + rounds - 1) / rounds);
+    const auto launch = [&](auto k, uint32_t *gmax, const float4 *sorted4) -> hipError_t {
+        return launch_lds<decltype(k)::value>(156 * 1024, dim3(blocks), dim3(kFrontThreads), front_shmem, s, r.lt, whole, go,
+                                              r.w.gT, r.coords, r.w.totals, r.w.cnt, r.n, r.NP, t_lb, t_le, ts_log2, rounds, gmax,
+                                              (uint32_t)cps16, sorted4);
+    };
+    if (sorted)   // (implies r.use_fx and counts)
+        return launch(KernelTag<&front16_kernel<DIM, T, F, true, true, true>>{}, r.w.gmax, r.sb->sorted4);
+    if (r.use_fx && counts) return launch(KernelTag<&front16_kernel<DIM, T, F, true, true>>{}, r.w.gmax, nullptr);
+    if (r.use_fx) return launch(KernelTag<&front16_kernel<DIM, T, F, true, false>>{}, r.w.gmax, nullptr);
+    if (counts) return launch(KernelTag<&front16_kernel<DIM, T, F, false, true>>{}, nullptr, nullptr);
+    return launch(KernelTag<&front16_kernel<DIM, T, F, false, false>>{}, nullptr, nullptr);
+}
+template <int DIM, int F, class... A> static hipError_t launch_front(const BinRun &r, A... a) {
+    return r.dtype == SHACIRA_F32 ? launch_front_as<DIM, float, F>(r, a...) : launch_front_as<DIM, __half, F>(r, a...);
+}
+
+// pass D: the direct levels, one pass over the whole batch, no items (they add into the zeroed table). `from_gT`: the call
+// staged transposed gradients; else the kernel reads grad_output itself.
+// When nothing is transposed (every level is direct: the image configs) there is no gmax, and a pass of its own over
+// grad_output costs more than the faster atomics return (tried: a streaming abs-max kernel, 0.103 vs 0.082 ms on config
+// B): the direct kernel's workgroups take a pilot maximum over their own samples instead (direct_accumulate_kernel).
 template <int DIM, int F>
-static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_idx, const float *coords,
-                          const void *grad_out, float *acc, const BinWorkspace &w, int64_t n, hipStream_t s,
-                          bool zero_table, __half *half_table, bool *converted, const SortedBatch *sb) {
-    const int L = lt.num_lods;
-    const int64_t NP = level_pitch(n);
-    BinPlan whole;
-    const int acc_kib = choose_acc_kib(DIM, dtype, lt, n);
-    const bool oic = one_image_compact_rule(n);
-    const int64_t nb = bin_batch_samples(DIM, dtype, lt, n);
-    const bool multi = nb < n;
+static hipError_t launch_direct(const BinRun &r, const BinPlan &plan, bool from_gT, hipStream_t zs) {
+    // one level group (S1's level 0): ~512 workgroups measured best; several groups (the all-direct image tables,
+    // 128 KiB images = one resident workgroup per CU): 256 in total = one wave of workgroups, no tail
+    // (config B backward 65 vs 77 us, tools/attic/direct_blocks.py)
+    uint32_t bpg = (plan.ngroups > 1 ? 256u : 512u) / plan.ngroups;
+    const uint32_t need = (uint32_t)((r.n + 2047) / 2048);      // at least ~2 samples per thread each
+    if (bpg > need) bpg = need;
+    if (bpg < 1) bpg = 1;
+    const size_t acc_bytes = (size_t)plan.BR * F * sizeof(double);
+    const dim3 grid(bpg, plan.ngroups);
+    // a row receives at most (samples walked by one workgroup) x (corners) contributions. Fixed-point images always:
+    // scaled by the transposing pass's max |gradient| per level when there is one (gmax), else by the workgroup's own
+    // pilot maximum (all-direct tables, small batches: direct_accumulate_kernel; config C backward 0.84 -> 0.63 ms,
+    // B 0.056 -> 0.047, kodak.yaml-shaped 0.104 -> 0.082 against the fp64 images)
+    const int headroom = fx_headroom(((uint64_t)r.n / bpg + kConsumeThreads) * (1u << DIM));
+    const uint32_t *gm = (from_gT && r.use_fx) ? r.w.gmax : nullptr;
+    const auto launch = [&](auto k, const float *xyz, auto *g, int stride) -> hipError_t {
+        return launch_lds<decltype(k)::value>(16384 * sizeof(double), grid, dim3(kConsumeThreads), acc_bytes, zs, r.lt, plan,
+                                              r.first_idx, xyz, g, r.acc, r.n, r.NP, gm, headroom, stride);
+    };
+    if (from_gT)
+        return launch(KernelTag<&direct_accumulate_kernel<DIM, F, float, true, true>>{}, r.cptr, (const float *)r.w.gT, r.cstride);
+    if (r.dtype == SHACIRA_F32)
+        return launch(KernelTag<&direct_accumulate_kernel<DIM, F, float, false, true>>{}, r.coords,
+                      static_cast<const float *>(r.grad_out), DIM);
+    return launch(KernelTag<&direct_accumulate_kernel<DIM, F, __half, false, true>>{}, r.coords,
+                  static_cast<const __half *>(r.grad_out), DIM);
+}
+
+// largest dynamic LDS a scatter launch can ask for: one staging window of the tile's item units (+ the pad units of
+// line-aligned runs when the tile goes through in one window) and one bucket byte per unit
+template <class ItemT> static constexpr size_t stage_max(size_t tile_units) {
+    constexpr size_t split = ScatterSplit<ItemT>::value;
+    constexpr size_t padu = split != 1 ? 0 : sizeof(ItemT) == 16 ? SHACIRA_RUN_ALIGN / 16 - 1 : sizeof(ItemT) == 12 ? SHACIRA_RUN_ALIGN / 4 - 1
+                            : (SHACIRA_PAD_HALF && sizeof(ItemT) == 8) ? SHACIRA_RUN_ALIGN / 8 - 1 : 0;
+    return (tile_units / split + (size_t)kMaxLevelBuckets * padu) * (sizeof(ItemT) + 1);
+}
+
+// pass B: samples [s0, hi) of the call. `done`: an event the launch signals on completion (hipExtLaunchKernelGGL's stop event),
+// or nullptr
+template <int DIM, int F, int FMT, bool STREAM>
+static hipError_t launch_scatter_as(const BinRun &r, const BinPlan &plan, uint32_t cps, int64_t s0, int64_t hi, float *zacc,
+                                    hipStream_t s, hipEvent_t done) {
+    using ItemT = typename ItemSel<F, FMT>::type;
+    constexpr auto kernel = &bin_scatter_kernel<DIM, F, FMT, STREAM>;
+    constexpr size_t tile_units = (size_t)TileOf<DIM>::value << (DIM - 1);
+    // (one staging window: the tile's items + the pad units of its runs, plan.stage_cap; windows: exact runs, 1 / split of the tile)
+    constexpr size_t split = ScatterSplit<ItemT>::value;
+    const size_t shmem = (split == 1 ? (size_t)plan.stage_cap : tile_units / split) * (sizeof(ItemT) + 1);
+#ifdef SCATTER_LEVEL_FAST
+    const dim3 grid(plan.nbl, plan.num_tiles);
+#else
+    const dim3 grid(plan.num_tiles, plan.nbl);
+#endif
+    const dim3 block(ScatterThreads<DIM, F, FMT>::value);
+    ItemT *items = reinterpret_cast<ItemT *>(r.w.items);
+    SHACIRA_CHECK(lds_opt_in<kernel>(stage_max<ItemT>(tile_units)));
+    if (done != nullptr)
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)shmem, s, nullptr, done, 0u, r.lt, plan, r.cptr, (const float *)r.w.gT,
+                              (const uint64_t *)r.w.base, (const uint32_t *)r.w.cnt, cps, items, s0, hi, r.NP, zacc, r.first_idx,
+                              (const uint32_t *)r.w.unit_first, r.cstride);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, shmem, s, r.lt, plan, r.cptr, r.w.gT, r.w.base, r.w.cnt, cps, items, s0, hi, r.NP,
+                           zacc, r.first_idx, r.w.unit_first, r.cstride);
+    return hipGetLastError();
+}
+template <int DIM, int F, class... A> static hipError_t launch_scatter(const BinRun &r, int fmt, A... a) {
+    if (fmt == 2) {
+        if constexpr (DIM == 3 && F == 2) return launch_scatter_as<DIM, F, 2, true>(r, a...);
+        return hipSuccess;
+    }
+    if (fmt == 1) return launch_scatter_as<DIM, F, 1, true>(r, a...);
+    if (r.use_fx) return launch_scatter_as<DIM, F, 0, true>(r, a...);
+    // batches below 2^17 samples: plain item stores, the consume pass reads them back from the caches
+    return launch_scatter_as<DIM, F, 0, false>(r, a...);
+}
+
+// pass C. `wc`: the persistent form's work counter or nullptr; `hout`: the caller's half table for single-unit buckets or nullptr
+template <int F, bool FX, int FMT>
+static hipError_t launch_consume_as(const BinRun &r, const BinPlan &plan, uint32_t grid_units, int force_atomic, int headroom,
+                                    uint32_t *wc, __half *hout, hipStream_t s) {
+    using ItemT = typename ItemSel<F, FMT>::type;
+    return launch_lds<&bin_consume_kernel<F, FX, FMT>>(16384 * sizeof(double), dim3(grid_units), dim3(kConsumeThreads),
+                                                       (size_t)plan.BR * F * sizeof(double), s, r.lt, plan, r.first_idx,
+                                                       r.w.unit_first, r.w.unit_desc, reinterpret_cast<const ItemT *>(r.w.items),
+                                                       r.acc, force_atomic, headroom, wc, hout);
+}
+template <int DIM, int F, class... A> static hipError_t launch_consume(const BinRun &r, int fmt, A... a) {
+    if (fmt == 2) {
+        if constexpr (DIM == 3 && F == 2) return launch_consume_as<F, true, 2>(r, a...);
+        return hipSuccess;
+    }
+    if (fmt == 1) return r.use_fx ? launch_consume_as<F, true, 1>(r, a...) : launch_consume_as<F, false, 1>(r, a...);
+    return r.use_fx ? launch_consume_as<F, true, 0>(r, a...) : launch_consume_as<F, false, 0>(r, a...);
+}
+
+// the brick pass on stream `bs` (its images fit 64 KiB of LDS, resolve_brick: no opt-in). `done`: as for the scatter pass
+template <int DIM, int F>
+static hipError_t launch_brick(const BinRun &r, const BrickPlan &brick, hipStream_t bs, hipEvent_t done) {
+    if constexpr (DIM == 3) {
+        const size_t img = (size_t)brick.rows_total * F * sizeof(double);
+        const int hr = fx_headroom((uint64_t)kBrickUnit * 8u);
+        // one workgroup per group (its first unit) + one per kBrickUnit-record window of the batch (what over-full groups
+        // hold beyond; all of them leave at once on a uniform batch)
+        const uint32_t groups = brick.groups_x * (uint32_t)(brick.nb[1] * brick.nb[2]);
+        const uint32_t windows = (uint32_t)((r.n + kBrickUnit - 1) / kBrickUnit);
+        if (done != nullptr)
+            hipExtLaunchKernelGGL((brick_accumulate_kernel<F>), dim3(groups + windows), dim3(kBrickThreads), (uint32_t)img, bs,
+                                  nullptr, done, 0u, r.lt, brick, r.first_idx, r.sb->sorted4, r.sb->block_start,
+                                  (const float *)r.w.gT, r.NP, r.acc, (const uint32_t *)r.w.gmax, hr);
+        else
+            hipLaunchKernelGGL((brick_accumulate_kernel<F>), dim3(groups + windows), dim3(kBrickThreads), img, bs, r.lt, brick,
+                               r.first_idx, r.sb->sorted4, r.sb->block_start, r.w.gT, r.NP, r.acc, r.w.gmax, hr);
+        return hipGetLastError();
+    } else {
+        return hipSuccess;
+    }
+}
+
+// The launch sequence of a resolved call: zeroing and control words, front / transpose pass, direct levels, per sub-batch
+// count - scan - scatter - consume, brick pass, half conversion. Policy that needs the pointers or the stream (which passes
+// run, on which stream, fused with what) is decided here; everything a workspace query can see was decided by bin_resolve.
+template <int DIM, int F>
+static hipError_t run_bin(const BinCall &call, const LevelTable &lt, const int32_t *first_idx, const float *coords,
+                          const void *grad_out, float *acc, const BinWorkspace &w, hipStream_t s, bool zero_table,
+                          __half *half_table, bool *converted, const SortedBatch *sb) {
+    const int dtype = call.dtype, L = lt.num_lods, fmt = call.fmt;
+    const int64_t n = call.n, nb = call.nb;
+    const bool multi = call.multi;
+    const BrickPlan &brick = call.brick;
     const bool stage_all = (lt.stage_flags & SHACIRA_BWD_STAGE_ALL_LEVELS) != 0;
     const bool staged = (lt.stage_flags & SHACIRA_BWD_REUSE_STAGED) != 0;
-    // Brick pass (bwd_brick.h): with the batch's plan at hand (the cell-sorted forward's records), coarse 3-D levels are
-    // accumulated block by block in LDS and leave the item stream. Whole calls over one sub-batch that accumulate in
-    // fixed point (>= 2^17 samples: the regime the item stream binds in); never for tables whose levels are all direct.
-    BrickPlan brick;
-    uint32_t skip_mask = 0;
-    brick_levels_of_call(DIM, dtype, lt, n, sb, zero_table, (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0, brick, skip_mask);
-    make_plan(DIM, dtype, lt, n, whole, acc_kib, oic, skip_mask, n);
-    // SORTED mode: the whole call walks the batch in the plan's block order -- the front kernel gathers the gradient rows in
-    // that order, so gT and every later pass's sample index mean "k-th sorted sample" and coordinates come from the records
+    BinPlan whole;
+    make_plan(call, lt, n, whole, call.skip_mask);
+    // SORTED mode (the call has a brick pass): the whole call walks the batch in the plan's block order -- the front kernel
+    // gathers the gradient rows in that order, so gT and every later pass's sample index mean "k-th sorted sample" and
+    // coordinates come from the records
     const bool sorted = brick.nlev > 0;
-    const float *cptr = sorted ? reinterpret_cast<const float *>(sb->sorted4) : coords;
-    const int cstride = sorted ? 4 : DIM;
     // Where the brick pass runs (it is bound by LDS atomics and touches HBM hardly at all; it needs the zeroed table, the
     // sorted gT and gmax, i.e. the front pass): option bwd_brick_fork 0 = last on the caller's stream (behind the scatter pass,
     // which wants the transposed gradients still in the Infinity Cache); 1 / 2 = on the side stream, forked behind the front pass /
@@ -677,44 +931,18 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
     // room for brick workgroups on every CU and wait on HBM while the LDS atomic units idle
     int brick_mode = -1;   // -1: no brick pass
     SideStream *bss = nullptr;
-    if (brick.nlev > 0) {
+    if (sorted) {
         brick_mode = opt().bwd_brick_fork;
         if (brick_mode > 0) SHACIRA_CHECK(side_stream(&bss));
     }
-    // `done`: an event the launch signals on completion (hipExtLaunchKernelGGL's stop event), or nullptr
-    auto launch_brick = [&](hipStream_t bs, hipEvent_t done = nullptr) -> hipError_t {
-        if constexpr (DIM == 3) {
-            const size_t img = (size_t)brick.rows_total * F * sizeof(double);
-            const int hr = fx_headroom((uint64_t)kBrickUnit * 8u);
-            // one workgroup per group (its first unit) + one per kBrickUnit-record window of the batch (what over-full groups
-            // hold beyond; all of them leave at once on a uniform batch)
-            const uint32_t groups = brick.groups_x * (uint32_t)(brick.nb[1] * brick.nb[2]);
-            const uint32_t windows = (uint32_t)((n + kBrickUnit - 1) / kBrickUnit);
-            if (done != nullptr)
-                hipExtLaunchKernelGGL((brick_accumulate_kernel<F>), dim3(groups + windows), dim3(kBrickThreads), (uint32_t)img, bs,
-                                      nullptr, done, 0u, lt, brick, first_idx, sb->sorted4, sb->block_start, (const float *)w.gT,
-                                      NP, acc, (const uint32_t *)w.gmax, hr);
-            else
-                hipLaunchKernelGGL((brick_accumulate_kernel<F>), dim3(groups + windows), dim3(kBrickThreads), img, bs, lt, brick,
-                                   first_idx, sb->sorted4, sb->block_start, w.gT, NP, acc, w.gmax, hr);
-            return hipGetLastError();
-        } else {
-            (void)bs;
-            return hipSuccess;
-        }
-    };
-    auto fork_brick = [&]() -> hipError_t {
-        SHACIRA_CHECK(hipEventRecord(bss->bfork, s));
-        SHACIRA_CHECK(hipStreamWaitEvent(bss->stream, bss->bfork, 0));
-        SHACIRA_CHECK(launch_brick(bss->stream));
-        return hipEventRecord(bss->bjoin, bss->stream);
-    };
     // only binned levels consume the transposed gradients (a later call on this workspace may, too: stage_all) -- a table
     // whose levels are all direct has none in any level range, so its calls never stage (and carve() reserves no gT)
-    const bool need_T = whole.nbl > 0 || ((stage_all || staged) && !table_all_direct(DIM, dtype, lt, n));
+    const bool need_T = whole.nbl > 0 || ((stage_all || staged) && !call.all_direct);
     // fixed-point images pay off once the accumulation itself dominates; small batches are bound by fixed costs and
     // keep the fp64 image (and skip the gmax bookkeeping): measured 100 vs 107 us at 65 536 samples
     const bool use_fx = need_T && n >= SHACIRA_FX_MIN;
+    const BinRun r{lt, w, first_idx, coords, grad_out, acc, dtype, n, level_pitch(n), use_fx,
+                   sorted ? reinterpret_cast<const float *>(sb->sorted4) : coords, sorted ? 4 : DIM, sb};
     // the 16-byte front kernel needs rows of whole 16-byte vectors and a 16-byte aligned input
     const size_t esz = dtype == SHACIRA_F32 ? 4 : 2;
     const int kvec = (int)(16 / (esz * F));
@@ -726,8 +954,8 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
     // fp16 tables, one sub-batch over all levels: single-unit hashed buckets flush straight into the caller's half table and
     // the conversion of the fp32 accumulation image skips them (f32_to_f16_skip_kernel) -- most of the table never makes the
     // round trip through the image (round 4)
-    const bool direct_half = half_table != nullptr && half_items(dtype, lt) && !multi && !stage_all && !staged &&
-                             whole.nbl > 0 && lt.level_begin == 0 && lt.level_end == L;
+    const bool direct_half = half_table != nullptr && fmt == 1 && !multi && !stage_all && !staged && whole.nbl > 0 &&
+                             lt.level_begin == 0 && lt.level_end == L;
     // side stream (option bwd_fork): table zeroing + direct levels beside the critical path. Worth an event pair once the
     // batch is large (threshold in units of n * L * F: heavier tables fork earlier)
     const int64_t fork_work = n * lt.num_lods * lt.feature_dim;
@@ -739,15 +967,22 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
     bool any_hashed = false;
     for (uint32_t q = 0; q < whole.nbl; ++q) any_hashed = any_hashed || lt.dense[whole.blevel[q]] == 0;
     const bool selective = zero_table && !multi && any_hashed && opt().bwd_selective_zero != 0;
+    SideJoin zjoin(s), bjoin(s);   // table zeroing + direct levels; brick pass
     SideStream *ss = nullptr;
     hipStream_t zs = s;   // stream of the table zeroing and the direct levels
     if (fork) {
         SHACIRA_CHECK(side_stream(&ss));
-        SHACIRA_CHECK(hipEventRecord(ss->fork, s));
-        SHACIRA_CHECK(hipStreamWaitEvent(ss->stream, ss->fork, 0));
+        SHACIRA_CHECK(zjoin.fork(ss->stream, ss->fork, ss->join));
         zs = ss->stream;
     }
-    // bucket totals (and, when this call transposes, the per-level max |grad_output| right behind them) start at zero
+    const auto fork_brick = [&]() -> hipError_t {
+        SHACIRA_CHECK(bjoin.fork(bss->stream, bss->bfork, bss->bjoin));
+        SHACIRA_CHECK((launch_brick<DIM, F>(r, brick, bss->stream, nullptr)));
+        return bjoin.record();
+    };
+
+    // 1. zeroing and control words: bucket totals (and, when this call transposes, the per-level max |grad_output| right behind
+    // them) start at zero
     const bool need_words = whole.nbl > 0 || (!staged && use_fx);
     const uint32_t words = (uint32_t)kTotalShards * kMaxBuckets + ((!staged && use_fx) ? SHACIRA_MAX_LODS : 0);
     bool words_done = false;
@@ -766,122 +1001,26 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
         hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, w.totals, words);
         SHACIRA_CHECK_LAUNCH();
     }
-    if (need_T && !staged) {
-        const int t_lb = stage_all ? 0 : lt.level_begin, t_le = stage_all ? L : lt.level_end;
-        if (t16) {
-            // ~512 workgroups (two per CU, all resident) when the batch allows; never fewer than one tile per workgroup
-            const int64_t tiles = (n + ts16 - 1) / ts16;
-            int ts_log2 = 7;
-            while ((1 << ts_log2) < ts16) ++ts_log2;
-            int rounds = (int)((tiles + 511) / 512);
-            // padded runs: a workgroup's counting tiles must be whole scatter tiles (the pad units are per scatter tile)
-            const int cps16 = TileOf<DIM>::value / ts16;
-            if (whole.pad > 1u && front_counts) rounds = (rounds + cps16 - 1) / cps16 * cps16;
-            const uint32_t blocks = (uint32_t)((tiles + rounds - 1) / rounds);
-#define SHACIRA_FRONT(TT, GM, CN)                                                                                         \
-            hipLaunchKernelGGL((front16_kernel<DIM, TT, F, GM, CN>), dim3(blocks), dim3(kFrontThreads), front_shmem, s, lt, \
-                               whole, static_cast<const TT *>(grad_out), w.gT, coords, w.totals, w.cnt, n, NP, t_lb, t_le, ts_log2, \
-                               rounds, GM ? w.gmax : nullptr, (uint32_t)cps16)
-#define SHACIRA_FRONT_SORTED(TT)                                                                                          \
-            hipLaunchKernelGGL((front16_kernel<DIM, TT, F, true, true, true>), dim3(blocks), dim3(kFrontThreads), front_shmem, s, lt, \
-                               whole, static_cast<const TT *>(grad_out), w.gT, coords, w.totals, w.cnt, n, NP, t_lb, t_le, ts_log2, \
-                               rounds, w.gmax, (uint32_t)cps16, sb->sorted4)
-            if (sorted) {   // (implies use_fx and front_counts)
-                if (dtype == SHACIRA_F32) SHACIRA_FRONT_SORTED(float);
-                else SHACIRA_FRONT_SORTED(__half);
-            } else if (dtype == SHACIRA_F32) {
-                if (use_fx && front_counts) SHACIRA_FRONT(float, true, true);
-                else if (use_fx) SHACIRA_FRONT(float, true, false);
-                else if (front_counts) SHACIRA_FRONT(float, false, true);
-                else SHACIRA_FRONT(float, false, false);
-            } else {
-                if (use_fx && front_counts) SHACIRA_FRONT(__half, true, true);
-                else if (use_fx) SHACIRA_FRONT(__half, true, false);
-                else if (front_counts) SHACIRA_FRONT(__half, false, true);
-                else SHACIRA_FRONT(__half, false, false);
-            }
-#undef SHACIRA_FRONT
-#undef SHACIRA_FRONT_SORTED
-        } else {
-            const uint32_t blocks = (uint32_t)((n + 255) / 256);
-            const size_t shmem = (size_t)256 * (L + 1) * F * sizeof(float);
-            if (dtype == SHACIRA_F32 && use_fx)
-                hipLaunchKernelGGL((transpose_grad_kernel<float, F, true>), dim3(blocks), dim3(256), shmem, s,
-                                   static_cast<const float *>(grad_out), w.gT, n, NP, L, t_lb, t_le, w.gmax);
-            else if (dtype == SHACIRA_F32)
-                hipLaunchKernelGGL((transpose_grad_kernel<float, F, false>), dim3(blocks), dim3(256), shmem, s,
-                                   static_cast<const float *>(grad_out), w.gT, n, NP, L, t_lb, t_le, nullptr);
-            else if (use_fx)
-                hipLaunchKernelGGL((transpose_grad_kernel<__half, F, true>), dim3(blocks), dim3(256), shmem, s,
-                                   static_cast<const __half *>(grad_out), w.gT, n, NP, L, t_lb, t_le, w.gmax);
-            else
-                hipLaunchKernelGGL((transpose_grad_kernel<__half, F, false>), dim3(blocks), dim3(256), shmem, s,
-                                   static_cast<const __half *>(grad_out), w.gT, n, NP, L, t_lb, t_le, nullptr);
-        }
-        SHACIRA_CHECK_LAUNCH();
-    }
+    // 2. front or transpose pass
+    if (need_T && !staged)
+        SHACIRA_CHECK((launch_front<DIM, F>(r, whole, t16 ? ts16 : 0, front_shmem, front_counts, sorted, stage_all ? 0 : lt.level_begin,
+                                            stage_all ? L : lt.level_end, s)));
     if (fork) {   // the direct levels need the staged gradients (and gmax)
         SHACIRA_CHECK(hipEventRecord(ss->staged, s));
         SHACIRA_CHECK(hipStreamWaitEvent(ss->stream, ss->staged, 0));
     }
     if (brick_mode == 1) SHACIRA_CHECK(fork_brick());
-    // When nothing is transposed (every level is direct: the image configs) there is no gmax, and a pass of its own over
-    // grad_output costs more than the faster atomics return (tried: a streaming abs-max kernel, 0.103 vs 0.082 ms on config
-    // B): the direct kernel's workgroups take a pilot maximum over their own samples instead (direct_accumulate_kernel).
-    // direct levels: one pass over the whole batch, no items (they add into the zeroed table)
-    if (whole.ngroups > 0) {
-        const BinPlan &plan = whole;
-        // one level group (S1's level 0): ~512 workgroups measured best; several groups (the all-direct image tables,
-        // 128 KiB images = one resident workgroup per CU): 256 in total = one wave of workgroups, no tail
-        // (config B backward 65 vs 77 us, tools/attic/direct_blocks.py)
-        uint32_t bpg = (plan.ngroups > 1 ? 256u : 512u) / plan.ngroups;
-        const uint32_t need = (uint32_t)((n + 2047) / 2048);      // at least ~2 samples per thread each
-        if (bpg > need) bpg = need;
-        if (bpg < 1) bpg = 1;
-        const size_t acc_bytes = (size_t)plan.BR * F * sizeof(double);
-        const dim3 grid(bpg, plan.ngroups);
-        // a row receives at most (samples walked by one workgroup) x (corners) contributions. Fixed-point images always:
-        // scaled by the transposing pass's max |gradient| per level when there is one (gmax), else by the workgroup's own
-        // pilot maximum (all-direct tables, small batches: direct_accumulate_kernel; config C backward 0.84 -> 0.63 ms,
-        // B 0.056 -> 0.047, kodak.yaml-shaped 0.104 -> 0.082 against the fp64 images)
-        const int headroom = fx_headroom(((uint64_t)n / bpg + kConsumeThreads) * (1u << DIM));
-        const uint32_t *gm = (need_T && use_fx) ? w.gmax : nullptr;
-        if (need_T)
-            hipLaunchKernelGGL((direct_accumulate_kernel<DIM, F, float, true, true>), grid, dim3(kConsumeThreads),
-                               acc_bytes, zs, lt, plan, first_idx, cptr, w.gT, acc, n, NP, gm, headroom, cstride);
-        else if (dtype == SHACIRA_F32)
-            hipLaunchKernelGGL((direct_accumulate_kernel<DIM, F, float, false, true>), grid, dim3(kConsumeThreads),
-                               acc_bytes, zs, lt, plan, first_idx, coords, static_cast<const float *>(grad_out), acc, n,
-                               NP, gm, headroom);
-        else
-            hipLaunchKernelGGL((direct_accumulate_kernel<DIM, F, __half, false, true>), grid, dim3(kConsumeThreads),
-                               acc_bytes, zs, lt, plan, first_idx, coords, static_cast<const __half *>(grad_out), acc, n,
-                               NP, gm, headroom);
-        SHACIRA_CHECK_LAUNCH();
-    }
-    if (fork) SHACIRA_CHECK(hipEventRecord(ss->join, ss->stream));
+    // 3. direct levels
+    if (whole.ngroups > 0) SHACIRA_CHECK((launch_direct<DIM, F>(r, whole, need_T, zs)));
+    if (fork) SHACIRA_CHECK(zjoin.record());
     if (whole.nbl == 0) return hipSuccess;   // (fork implies binned levels)
+    // 4. per sub-batch: count, scan, scatter, consume
     constexpr int NPAIR = 1 << (DIM - 1);
-    // half-precision item stream: fp16 tables with F = 2 (8-byte units)
-    const int fmt = item_format(DIM, dtype, lt, n);
-    const bool half = fmt == 1;
-    // (one staging window: the tile's items + the pad units of its runs, plan.stage_cap; windows: exact runs, 1 / split of the tile)
-    auto stage_bytes = [&](const BinPlan &pl) -> size_t {
-        const size_t isz = fmt == 2 ? sizeof(Item12) : half ? sizeof(typename ItemSel<F, true>::type) : sizeof(Item<F>);
-        const int split = half ? ScatterSplit<typename ItemSel<F, true>::type>::value : ScatterSplit<Item<F>>::value;
-        const size_t units = split == 1 ? (size_t)pl.stage_cap : (size_t)TileOf<DIM>::value * NPAIR / split;
-        return units * (isz + 1);
-    };
-#ifdef SCATTER_LEVEL_FAST
-#define SCATTER_GRID(pl) dim3((pl).nbl, (pl).num_tiles)
-#else
-#define SCATTER_GRID(pl) dim3((pl).num_tiles, (pl).nbl)
-#endif
     bool first_batch = true;
     for (int64_t s0 = 0; s0 < n; s0 += nb) {
         const int64_t hi = (s0 + nb < n) ? (s0 + nb) : n;
         BinPlan plan;
-        make_plan(DIM, dtype, lt, hi - s0, plan, acc_kib, oic, skip_mask, n);
+        make_plan(call, lt, hi - s0, plan, call.skip_mask);
         if (!first_batch) {
             hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, w.totals, (uint32_t)kTotalShards * kMaxBuckets);
             SHACIRA_CHECK_LAUNCH();
@@ -901,49 +1040,22 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
                            dim3(kScanThreads), 0, s, w.totals, w.base, w.unit_first, w.unit_desc, plan.total_buckets, plan,
                            w.work_counter, use_fx ? w.gmax : nullptr, w.cnt, cps, cnt_rows);
         SHACIRA_CHECK_LAUNCH();
+        // Brick pass beside the consume pass: the event the side stream waits for rides on the scatter kernel's own
+        // completion signal (hipExtLaunchKernelGGL's stop event) instead of a marker of its own behind it -- that marker
+        // kept the consume pass from being staged behind the scatter pass (7.6 us between the two under the profiler).
+        // Not while the stream is being captured into a graph (plain launch + event record there).
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        const bool fork_signalled = fmt == 2 && brick_mode == 2 && opt().bwd_ext_fork != 0 &&
+                                    hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
         // (selective zeroing: hashed buckets with 0 or several units are zeroed by the scatter pass's tail)
-        float *zacc = selective ? acc : nullptr;
-        bool fork_signalled = false;   // the scatter launch itself signals the brick pass's fork event (below)
-        if (fmt == 2) {
-            if constexpr (DIM == 3 && F == 2) {
-                // Brick pass beside the consume pass: the event the side stream waits for rides on the scatter kernel's own
-                // completion signal (hipExtLaunchKernelGGL's stop event) instead of a marker of its own behind it -- that marker
-                // kept the consume pass from being staged behind the scatter pass (7.6 us between the two under the profiler).
-                // Not while the stream is being captured into a graph (plain launch + event record there).
-                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                if (brick_mode == 2 && opt().bwd_ext_fork != 0 && hipStreamIsCapturing(s, &cap) == hipSuccess &&
-                    cap == hipStreamCaptureStatusNone) {
-                    hipExtLaunchKernelGGL((bin_scatter_kernel<DIM, F, 2>), SCATTER_GRID(plan),
-                                          dim3(ScatterThreads<DIM, F, 2>::value), (uint32_t)stage_bytes(plan), s, nullptr,
-                                          bss->bfork, 0u, lt, plan, cptr, (const float *)w.gT, (const uint64_t *)w.base, (const uint32_t *)w.cnt, cps,
-                                          reinterpret_cast<Item12 *>(w.items), s0, hi, NP, zacc, first_idx,
-                                          (const uint32_t *)w.unit_first, cstride);
-                    fork_signalled = true;
-                } else {
-                    hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, 2>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 2>::value),
-                                       stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
-                                       reinterpret_cast<Item12 *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
-                }
-            }
-        } else if (half)
-            hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, true>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 1>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
-                               reinterpret_cast<typename ItemSel<F, true>::type *>(w.items), s0, hi, NP, zacc, first_idx,
-                               w.unit_first, cstride);
-        else if (use_fx)
-            hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, false>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 0>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
-                               reinterpret_cast<Item<F> *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
-        else   // batches below 2^17 samples: plain item stores, the consume pass reads them back from the caches
-            hipLaunchKernelGGL((bin_scatter_kernel<DIM, F, false, false>), SCATTER_GRID(plan), dim3(ScatterThreads<DIM, F, 0>::value),
-                               stage_bytes(plan), s, lt, plan, cptr, w.gT, w.base, w.cnt, cps,
-                               reinterpret_cast<Item<F> *>(w.items), s0, hi, NP, zacc, first_idx, w.unit_first, cstride);
-        SHACIRA_CHECK_LAUNCH();
-        if (fork) SHACIRA_CHECK(hipStreamWaitEvent(s, ss->join, 0));   // table zeroed, direct levels in
+        SHACIRA_CHECK((launch_scatter<DIM, F>(r, fmt, plan, cps, s0, hi, selective ? acc : nullptr, s,
+                                              fork_signalled ? bss->bfork : nullptr)));
+        if (fork) SHACIRA_CHECK(zjoin.wait());   // table zeroed, direct levels in
         if (brick_mode == 2) {
             if (fork_signalled) {
-                SHACIRA_CHECK(hipStreamWaitEvent(bss->stream, bss->bfork, 0));
-                SHACIRA_CHECK(launch_brick(bss->stream, bss->bjoin));   // (and the join event on the brick launch)
+                SHACIRA_CHECK(bjoin.fork(bss->stream, bss->bfork, bss->bjoin, true));
+                SHACIRA_CHECK((launch_brick<DIM, F>(r, brick, bss->stream, bss->bjoin)));   // (and the join event on the brick launch)
+                bjoin.signalled();
             } else {
                 SHACIRA_CHECK(fork_brick());
             }
@@ -951,39 +1063,18 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
         const uint64_t max_items = (uint64_t)(hi - s0) * plan.nbl * NPAIR +
                                    (uint64_t)plan.num_tiles * plan.total_buckets * (plan.pad - 1u);
         uint32_t grid_units = (uint32_t)(max_items / plan.chunk_min) + plan.total_buckets + 1;
-        const size_t acc_bytes = (size_t)plan.BR * F * sizeof(double);
         // persistent: as many workgroups as the chip holds fetch units from the work counter (measured: S1 backward
         // 0.611 -> 0.595 ms, 2-D 0.375 -> 0.369; with the fetch pipelined one unit ahead also at 65 536 samples)
         uint32_t *wc = (opt().bwd_persistent != 0 && n >= SHACIRA_PERSIST_MIN) ? w.work_counter : nullptr;
         if (wc != nullptr && grid_units > 512u) grid_units = 512u;
         const int headroom = use_fx ? fx_headroom((uint64_t)plan.chunk + 1) : -1;   // a unit streams <= chunk items
-        const int fa = multi ? 1 : 0;
-        __half *hout = direct_half ? half_table : nullptr;
-        if (fmt == 2) {
-            if constexpr (DIM == 3 && F == 2)
-                hipLaunchKernelGGL((bin_consume_kernel<F, true, 2>), dim3(grid_units), dim3(kConsumeThreads), acc_bytes, s, lt,
-                                   plan, first_idx, w.unit_first, w.unit_desc, reinterpret_cast<const Item12 *>(w.items), acc,
-                                   fa, headroom, wc);
-        } else if (half && use_fx)
-            hipLaunchKernelGGL((bin_consume_kernel<F, true, true>), dim3(grid_units), dim3(kConsumeThreads), acc_bytes, s,
-                               lt, plan, first_idx, w.unit_first, w.unit_desc,
-                               reinterpret_cast<const typename ItemSel<F, true>::type *>(w.items), acc, fa, headroom, wc, hout);
-        else if (half)
-            hipLaunchKernelGGL((bin_consume_kernel<F, false, true>), dim3(grid_units), dim3(kConsumeThreads), acc_bytes, s,
-                               lt, plan, first_idx, w.unit_first, w.unit_desc,
-                               reinterpret_cast<const typename ItemSel<F, true>::type *>(w.items), acc, fa, headroom, wc, hout);
-        else if (use_fx)
-            hipLaunchKernelGGL((bin_consume_kernel<F, true, false>), dim3(grid_units), dim3(kConsumeThreads), acc_bytes, s, lt,
-                               plan, first_idx, w.unit_first, w.unit_desc,
-                               reinterpret_cast<const Item<F> *>(w.items), acc, fa, headroom, wc);
-        else if (!half)
-            hipLaunchKernelGGL((bin_consume_kernel<F, false, false>), dim3(grid_units), dim3(kConsumeThreads), acc_bytes, s, lt,
-                               plan, first_idx, w.unit_first, w.unit_desc,
-                               reinterpret_cast<const Item<F> *>(w.items), acc, fa, headroom, wc);
-        SHACIRA_CHECK_LAUNCH();
+        SHACIRA_CHECK((launch_consume<DIM, F>(r, fmt, plan, grid_units, multi ? 1 : 0, headroom, wc,
+                                              direct_half ? half_table : nullptr, s)));
     }
-    if (brick_mode == 0) SHACIRA_CHECK(launch_brick(s));   // LAST on the caller's stream
-    if (brick_mode > 0) SHACIRA_CHECK(hipStreamWaitEvent(s, bss->bjoin, 0));
+    // 5. brick pass, when it is not beside the item passes: LAST on the caller's stream
+    if (brick_mode == 0) SHACIRA_CHECK((launch_brick<DIM, F>(r, brick, s, nullptr)));
+    if (brick_mode > 0) SHACIRA_CHECK(bjoin.wait());
+    // 6. half conversion
     if (direct_half) {
         hipLaunchKernelGGL(f32_to_f16_skip_kernel, dim3(128, (uint32_t)L), dim3(256), 0, s, acc, half_table, first_idx, lt,
                            whole, w.unit_first, F);
@@ -993,84 +1084,18 @@ static hipError_t run_bin(int dtype, const LevelTable &lt, const int32_t *first_
     return hipSuccess;
 }
 
-// largest dynamic LDS a scatter launch can ask for: one staging window of the tile's item units (+ the pad units of
-// line-aligned runs when the tile goes through in one window) and one bucket byte per unit
-template <class ItemT> static constexpr size_t stage_max(size_t tile_units) {
-    constexpr size_t split = ScatterSplit<ItemT>::value;
-    constexpr size_t padu = split != 1 ? 0 : sizeof(ItemT) == 16 ? SHACIRA_RUN_ALIGN / 16 - 1 : sizeof(ItemT) == 12 ? SHACIRA_RUN_ALIGN / 4 - 1
-                            : (SHACIRA_PAD_HALF && sizeof(ItemT) == 8) ? SHACIRA_RUN_ALIGN / 8 - 1 : 0;
-    return (tile_units / split + (size_t)kMaxLevelBuckets * padu) * (sizeof(ItemT) + 1);
-}
-
-hipError_t bin_backward(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx, const float *coords,
-                        const void *grad_out, float *acc, void *workspace, int64_t n, hipStream_t s, bool zero_table,
-                        void *half_table, bool *converted, const SortedBatch *sb) {
+hipError_t bin_backward(const BinCall &call, const LevelTable &lt, const int32_t *first_idx, const float *coords,
+                        const void *grad_out, float *acc, void *workspace, hipStream_t s, bool zero_table, void *half_table,
+                        bool *converted, const SortedBatch *sb) {
     if (converted != nullptr) *converted = false;
-    __half *ht = (dtype == SHACIRA_F16) ? static_cast<__half *>(half_table) : nullptr;
-    BrickPlan brick;
-    uint32_t skip_mask = 0;
-    resolve_call(dim, dtype, lt, n, sb, zero_table, (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0, brick, skip_mask);
-    const BinWorkspace w = carve(dim, dtype, lt, n, workspace, carve_skip(dtype, skip_mask));
-    static PerDeviceOnce once;  // kernels that use more than 64 KiB of dynamic LDS must opt in once per device
-    const hipError_t attr_err = once.run([]() -> hipError_t {
-        hipError_t attr_err = hipSuccess;
-        // dynamic LDS actually requested (static LDS of the kernels comes on top and must fit in 160 KiB too)
-        auto set = [&attr_err](const void *fn, size_t bytes) {
-            if (bytes <= 64 * 1024 || bytes > 160 * 1024) return;   // (beyond the CU's LDS: such a launch fails by itself)
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e != hipSuccess) attr_err = e;
-        };
-#define SHACIRA_T_ATTR(TT, FF)                                                                           \
-        set(reinterpret_cast<const void *>(&transpose_grad_kernel<TT, FF, true>), 140 * 1024);          \
-        set(reinterpret_cast<const void *>(&transpose_grad_kernel<TT, FF, false>), 140 * 1024);         \
-        set(reinterpret_cast<const void *>(&front16_kernel<2, TT, FF, true, true>), 156 * 1024);        \
-        set(reinterpret_cast<const void *>(&front16_kernel<2, TT, FF, true, false>), 156 * 1024);       \
-        set(reinterpret_cast<const void *>(&front16_kernel<2, TT, FF, false, true>), 156 * 1024);       \
-        set(reinterpret_cast<const void *>(&front16_kernel<2, TT, FF, false, false>), 156 * 1024);      \
-        set(reinterpret_cast<const void *>(&front16_kernel<3, TT, FF, true, true>), 156 * 1024);        \
-        set(reinterpret_cast<const void *>(&front16_kernel<3, TT, FF, true, false>), 156 * 1024);       \
-        set(reinterpret_cast<const void *>(&front16_kernel<3, TT, FF, false, true>), 156 * 1024);       \
-        set(reinterpret_cast<const void *>(&front16_kernel<3, TT, FF, false, false>), 156 * 1024);      \
-        set(reinterpret_cast<const void *>(&front16_kernel<3, TT, FF, true, true, true>), 156 * 1024);
-        SHACIRA_T_ATTR(float, 2) SHACIRA_T_ATTR(float, 4) SHACIRA_T_ATTR(__half, 2) SHACIRA_T_ATTR(__half, 4)
-#undef SHACIRA_T_ATTR
-#define SHACIRA_DIRECT_ATTR(D, FF)                                                                              \
-        set(reinterpret_cast<const void *>(&direct_accumulate_kernel<D, FF, float, true, true>), 16384 * sizeof(double));   \
-        set(reinterpret_cast<const void *>(&direct_accumulate_kernel<D, FF, float, false, true>), 16384 * sizeof(double));  \
-        set(reinterpret_cast<const void *>(&direct_accumulate_kernel<D, FF, __half, false, true>), 16384 * sizeof(double));
-        SHACIRA_DIRECT_ATTR(2, 2) SHACIRA_DIRECT_ATTR(2, 4) SHACIRA_DIRECT_ATTR(3, 2) SHACIRA_DIRECT_ATTR(3, 4)
-#undef SHACIRA_DIRECT_ATTR
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<2, true, 2>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 2, 2>), stage_max<Item12>(TileOf<3>::value << 2));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<2, true, false>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<4, true, false>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<2, false, false>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<4, false, false>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<2, true, true>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<2, false, true>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<4, true, true>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_consume_kernel<4, false, true>), 16384 * sizeof(double));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 2, true>), stage_max<ItemH>(TileOf<2>::value << 1));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 2, true>), stage_max<ItemH>(TileOf<3>::value << 2));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 4, true>), stage_max<typename ItemSel<4, true>::type>(TileOf<2>::value << (2 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 4, true>), stage_max<typename ItemSel<4, true>::type>(TileOf<3>::value << (3 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 2, false>), stage_max<Item<2>>(TileOf<2>::value << (2 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 4, false>), stage_max<Item<4>>(TileOf<2>::value << (2 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 2, false>), stage_max<Item<2>>(TileOf<3>::value << (3 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 4, false>), stage_max<Item<4>>(TileOf<3>::value << (3 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 2, false, false>), stage_max<Item<2>>(TileOf<2>::value << (2 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<2, 4, false, false>), stage_max<Item<4>>(TileOf<2>::value << (2 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 2, false, false>), stage_max<Item<2>>(TileOf<3>::value << (3 - 1)));
-        set(reinterpret_cast<const void *>(&bin_scatter_kernel<3, 4, false, false>), stage_max<Item<4>>(TileOf<3>::value << (3 - 1)));
-        return attr_err;
-    });
-    if (attr_err != hipSuccess) return attr_err;
-    if (dim == 3) {
-        return lt.feature_dim == 2 ? run_bin<3, 2>(dtype, lt, first_idx, coords, grad_out, acc, w, n, s, zero_table, ht, converted, sb)
-                                   : run_bin<3, 4>(dtype, lt, first_idx, coords, grad_out, acc, w, n, s, zero_table, ht, converted, sb);
+    __half *ht = (call.dtype == SHACIRA_F16) ? static_cast<__half *>(half_table) : nullptr;
+    const BinWorkspace w = carve(call, lt, workspace);
+    if (call.dim == 3) {
+        return lt.feature_dim == 2 ? run_bin<3, 2>(call, lt, first_idx, coords, grad_out, acc, w, s, zero_table, ht, converted, sb)
+                                   : run_bin<3, 4>(call, lt, first_idx, coords, grad_out, acc, w, s, zero_table, ht, converted, sb);
     }
-    return lt.feature_dim == 2 ? run_bin<2, 2>(dtype, lt, first_idx, coords, grad_out, acc, w, n, s, zero_table, ht, converted, nullptr)
-                               : run_bin<2, 4>(dtype, lt, first_idx, coords, grad_out, acc, w, n, s, zero_table, ht, converted, nullptr);
+    return lt.feature_dim == 2 ? run_bin<2, 2>(call, lt, first_idx, coords, grad_out, acc, w, s, zero_table, ht, converted, nullptr)
+                               : run_bin<2, 4>(call, lt, first_idx, coords, grad_out, acc, w, s, zero_table, ht, converted, nullptr);
 }
 
 }  // namespace shacira

@@ -80,7 +80,7 @@ size_t hashgrid_backward_workspace(int dim, int dtype, const LevelTable &lt, int
 size_t hashgrid_backward_workspace_planned(int dim, int dtype, const LevelTable &lt, int64_t n, bool grad_aligned);
 hipError_t hashgrid_backward_dispatch(int dim, int dtype, const LevelTable &lt, const int32_t *first_idx,
                                       const float *coords, const void *grad_out, void *grad_table, void *workspace,
-                                      size_t workspace_bytes, int64_t n, hipStream_t s, const void *plan = nullptr);
+                                      size_t workspace_bytes, int64_t n, hipStream_t s, const void *plan, bool *too_small);
 
 // triplane.hip: the planes of one call, by value in the kernel arguments ([3 * l + p], p = 0 fmx, 1 fmy, 2 fmz)
 struct TriplaneArgs {
@@ -427,7 +427,6 @@ struct Options {
 };
 const Options &opt();             // the calling thread's snapshot
 void options_snapshot();          // taken at every extern "C" entry point that reads options
-void options_resolve_item12(int value);   // a call's decision for the automatic setting (-1), into the calling thread's snapshot
 
 // The decoder MLP's ReLU (mlp.hip, mlp_mfma.hip) as torch.relu has it: a NaN stays a NaN (fmaxf returns the other operand).
 // llvm.maximum is IEEE 754-2019 maximum, one v_maximum3_f32 on gfx950; the select "z < 0 ? 0 : z" means the same but made the

@@ -132,3 +132,35 @@ def test_backward_workspace_is_sized_by_the_selected_path():
     # shapes without a plan / outside the brick pass's rule: the plain size
     assert L.shacira_hashgrid_backward_planned_workspace_bytes(dim, 65536, len(res), 2, bw, arr, T, _lib.F32) == query(dim, res, bw, 65536)
     assert L.shacira_hashgrid_backward_planned_workspace_bytes(dim, n, len(res), 2, bw, arr, T, _lib.F16) == query(dim, res, bw, n, dtype=_lib.F16)
+
+
+def test_backward_workspace_bytes_match_the_recorded_counts(golden):
+    """Every per-call decision of the binned backward (image size, sub-batch size, item format -- its tentative and final
+    order included --, one-image-compact rule, brick levels) shows in the two workspace queries, which are host code. Their
+    answers over tables x batch sizes x dtypes x option sets must equal, byte for byte, what tests/golden/
+    make_bwd_workspace_golden.py recorded before the call resolver was gathered into one function."""
+    g = golden("bwd_workspace_bytes.json")
+    L = _lib.lib()
+    assert len(g["rows"]) == len(g["tables"]) * 9 * 2 * len(g["option_sets"]) and len(g["option_sets"]) == 13
+    arrays = {name: (ctypes.c_int32 * len(res))(*res) for name, (_, res, _, _) in g["tables"].items()}
+    from conftest import table_layout
+    rows_T = {name: table_layout(res, bw, dim)[2] for name, (dim, res, bw, _) in g["tables"].items()}
+    bad = []
+    for k, opts in enumerate(g["option_sets"]):
+        saved = {name: _lib.get_option(name) for name in opts}
+        try:
+            for name, value in opts.items():
+                _lib.set_option(name, value)
+            for tname, n, dtype, kk, plain, planned in g["rows"]:
+                if kk != k:
+                    continue
+                dim, res, bw, F = g["tables"][tname]
+                args = (dim, n, len(res), F, bw, arrays[tname], rows_T[tname], dtype)
+                got = (L.shacira_hashgrid_backward_workspace_bytes(*args),
+                       L.shacira_hashgrid_backward_planned_workspace_bytes(*args))
+                if got != (plain, planned):
+                    bad.append((tname, n, dtype, opts, (plain, planned), got))
+        finally:
+            for name, value in saved.items():
+                _lib.set_option(name, value)
+    assert not bad, (len(bad), bad[:8])
