@@ -674,8 +674,9 @@ SHACIRA_API int shacira_mesh_sample(int mode, int64_t n, int64_t index_base, uin
  *   value    the mean of S over the (H - 10)(W - 10) VALID pixels -- at least 5 away from every border, so only windows that
  *            lie wholly inside the image count -- accumulated in fp64; then the plain mean over the channels
  *   borders  only the map sees them: G there reads the image through scipy's mode='reflect' (d c b a | a b c d | d c b a)
- * The fields are taken of x - mx and y - my, mx and my the pixel in the middle of the workgroup's tile (0 when it is not finite),
- * and the shift is added back to ux and uy: vx, vy and vxy do not change under a shift, but on a nearly flat image the
+ * The fields are taken of x - mx and y - my, one shift per (tile, channel) -- the median of the means of three rows of the tile
+ * (its centre row and the rows two and four above it, over the tile's columns and its left halo), so that no single pixel
+ * decides it; 0 when that is not finite -- and the shift is added back to ux and uy: vx, vy and vxy do not change under a shift, but on a nearly flat image the
  * cancellation in uxx - ux ux then leaves the differences of neighbouring pixels and not the rounding of their squares.
  * All arithmetic is fp32, one rounding per operator, except the window's taps, which are fused multiply-adds, summed from the
  * outer pair inwards: w5 (v[-5] + v[5]), then fma(w4, v[-4] + v[4], .), ..., the centre last. With x == y every S is exactly 1

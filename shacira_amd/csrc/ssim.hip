@@ -3,7 +3,7 @@
 // per-pixel score over the windows that lie wholly inside the image, the plain mean of that over the channels.
 //
 //   stencil    one workgroup per (tile of kSsimTh x kSsimTw pixels, channel). The tile and its 5-pixel halo of x and y go into
-//              LDS (border pixels by reflection, d c b a | a b c d; shifted by the tile's centre pixel, see below), the
+//              LDS (border pixels by reflection, d c b a | a b c d; shifted by the median of three row means, see below), the
 //              horizontal pass writes the five fields G x, G y, G xx, G yy, G xy of the 26 rows into LDS, the vertical pass
 //              keeps 14 rows of one column in registers and produces 4 pixels per lane. A wave reads one 64-float LDS row per instruction: 64 lanes, 64 banks. The
 //              forward instantiation turns the fields into the score S, adds the valid pixels of the tile in fp64 (lane
@@ -81,6 +81,30 @@ __device__ __forceinline__ float window11(const float *v, const SsimConst &k) {
     return fmaf(k.w[kRad], v[kRad], acc);
 }
 
+// the median of three; fminf / fmaxf return the operand that is a number, so one NaN among the three drops out
+__device__ __forceinline__ float median3(float a, float b, float c) {
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+}
+
+// v of another lane of the row of 16, by a DPP control: the add that takes it costs one VALU instruction and no LDS traffic
+template <int kCtrl>
+__device__ __forceinline__ float dpp_lane(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), kCtrl, 0xF, 0xF, true));
+}
+
+// the mean of v over the 64 lanes of the wave, wave-uniform. Every step adds a lane's partner to it and the partner adds the
+// lane, so the lanes of a row of 16 end with the same bits; the four rows are then added in one order.
+__device__ __forceinline__ float wave_mean(float v) {
+    v += dpp_lane<0xB1>(v);         // quad_perm [1, 0, 3, 2]
+    v += dpp_lane<0x4E>(v);         // quad_perm [2, 3, 0, 1]
+    v += dpp_lane<0x141>(v);        // row_half_mirror: the other quad of the eight
+    v += dpp_lane<0x140>(v);        // row_mirror: the other eight of the row
+    float row[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16 * i));
+    return ((row[0] + row[1]) + (row[2] + row[3])) * (1.f / 64.f);
+}
+
 // kGrad false: partials[ch * tiles + tile] = the fp64 sum of S over the tile's valid pixels; map (may be NULL) [H, W, C].
 // kGrad true:  planes [3][C][H][W] = dS/dux, dS/duxx, dS/duxy, zero outside the valid region.
 template <bool kGrad>
@@ -100,20 +124,56 @@ __global__ void __launch_bounds__(kSsimBlock) ssim_stencil_kernel(const float *_
         if (tid == 0) partials[(int64_t)ch * gridDim.x + tile] = 0.0;       // no valid pixel and no map to write
         return;
     }
-    // The fields are taken of x - mx and y - my, mx and my the tile's centre pixel: variance and covariance do not change under a
-    // shift, but the cancellation in uxx - ux * ux does -- on a nearly flat image it leaves the differences of neighbours, not
-    // the rounding of 0.49. The means get the shift back below. A centre that is not finite shifts by nothing, so a NaN stays
-    // inside its own window.
-    const int64_t mid = ((r0 + kTh / 2 < H ? r0 + kTh / 2 : H - 1) * W + (c0 + kTw / 2 < W ? c0 + kTw / 2 : W - 1)) * cin + ch;
-    float mx = x[mid], my = y[mid];
-    mx = fabsf(mx) < INFINITY ? mx : 0.f;
-    my = fabsf(my) < INFINITY ? my : 0.f;
-    for (int i = tid; i < kInH * kInW; i += kSsimBlock) {
+    // The fields are taken of x - mx and y - my: variance and covariance do not change under a shift, but the cancellation in
+    // uxx - ux * ux does -- on a nearly flat image it leaves the differences of neighbours, not the rounding of 0.49. The means
+    // get the shift back below. Any shift is valid, but the whole tile pays for a bad one. One pixel as the shift is bad twice:
+    // a pixel of 50 puts 1e-2 into the S of all the tile, one of 1e20 makes it NaN; and on an image around zero (pixels in
+    // [-1, 1]) a pixel is far from the mean, so ux = mx + G(x - mx) rounds at the size of mx, ten times what G(x) does. So mx is
+    // the median of three row means: the rows are the tile's centre row (clamped to the image) and the ones two and four rows
+    // above it, the columns the tile's with its left halo, inside the image -- at least six, the 64 lanes spread over them. A
+    // mean is near the tile's, where the shift serves the variances best and never costs the means more than itself; one pixel,
+    // whatever it holds, spoils one mean, and the median takes another (fminf / fmaxf pass over a NaN). A median that is still
+    // not finite shifts by nothing, so a NaN stays inside its own window. The rows lie in the tile or its halo: equal tiles of
+    // x and y shift alike. Every wave forms the same sums in the same order, and forward and backward do it here: one shift
+    // per tile.
+    const int64_t rc = r0 + kTh / 2 < H ? r0 + kTh / 2 : H - 1;                      // >= 8: the window fits the image
+    const int64_t lo = c0 > kRad ? c0 - kRad : 0, hi = c0 + kTw - 1 < W ? c0 + kTw - 1 : W - 1;
+    const int64_t pc = lo + (((tid & 63) * (int)(hi - lo + 1)) >> 6);              // the 64 lanes spread over lo .. hi
+    float px[3], py[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        const int64_t at = ((rc - 2 * g) * W + pc) * cin + ch;
+        px[g] = x[at];
+        py[g] = y[at];
+    }
+    // A lane's loads of the tile, all of them in flight behind the probes', then one wait: as a loop that loads, waits and
+    // stores, the staging is eight memory round trips in a row, and the probes would be a ninth.
+    constexpr int kStage = (kInH * kInW + kSsimBlock - 1) / kSsimBlock;        // 8, the last one partial
+    float tx[kStage], ty[kStage];
+#pragma unroll
+    for (int j = 0; j < kStage; ++j) {
+        const int i = tid + j * kSsimBlock < kInH * kInW ? tid + j * kSsimBlock : kInH * kInW - 1;
         const int r = i / kInW, c = i % kInW;
         const int64_t gr = reflect_index(r0 - kRad + r, H), gc = reflect_index(c0 - kRad + c, W);
         const int64_t at = (gr * W + gc) * cin + ch;
-        sx[r][c] = x[at] - mx;
-        sy[r][c] = y[at] - my;
+        tx[j] = x[at];
+        ty[j] = y[at];
+    }
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        px[g] = wave_mean(px[g]);
+        py[g] = wave_mean(py[g]);
+    }
+    float mx = median3(px[0], px[1], px[2]), my = median3(py[0], py[1], py[2]);
+    mx = fabsf(mx) < INFINITY ? mx : 0.f;
+    my = fabsf(my) < INFINITY ? my : 0.f;
+#pragma unroll
+    for (int j = 0; j < kStage; ++j) {
+        const int i = tid + j * kSsimBlock;
+        if (i < kInH * kInW) {
+            sx[i / kInW][i % kInW] = tx[j] - mx;
+            sy[i / kInW][i % kInW] = ty[j] - my;
+        }
     }
     __syncthreads();
     for (int i = tid; i < kInH * kTw; i += kSsimBlock) {

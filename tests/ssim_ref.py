@@ -17,9 +17,11 @@ def window():
     return gaussian_filter(e, sigma=SIGMA, truncate=TRUNCATE, mode="reflect")[RADIUS:-RADIUS]
 
 
-def ssim(a, b, dtype=np.float64, data_range=1.0):
+def ssim(a, b, dtype=np.float64, data_range=1.0, shift=False):
     """(value, map): a, b [H, W, C]; every step in `dtype`, the mean of the valid pixels in fp64, then the mean of the channels.
-    map is [H, W, C] in `dtype` with 'reflect' borders."""
+    map is [H, W, C] in `dtype` with 'reflect' borders. With `shift` the five fields are taken of a - sa and b - sb, sa and sb
+    the channel's image means rounded to `dtype`: variance and covariance do not change under a shift, the means get it back.
+    The same definition (to rounding in fp64), without the cancellation of uxx - ux * ux on an image far from zero."""
     a, b = np.asarray(a, dtype), np.asarray(b, dtype)
     if a.shape != b.shape or a.ndim != 3:
         raise ValueError("two [H, W, C] images of one shape")
@@ -31,9 +33,14 @@ def ssim(a, b, dtype=np.float64, data_range=1.0):
     values, maps = [], []
     for ch in range(a.shape[2]):
         x, y = a[..., ch], b[..., ch]
+        if shift:
+            sa, sb = dtype(x.mean(dtype=np.float64)), dtype(y.mean(dtype=np.float64))
+            x, y = x - sa, y - sb
         ux, uy = G(x), G(y)
         uxx, uyy, uxy = G(x * x), G(y * y), G(x * y)
         vx, vy, vxy = cov * (uxx - ux * ux), cov * (uyy - uy * uy), cov * (uxy - ux * uy)
+        if shift:
+            ux, uy = sa + ux, sb + uy
         a1, a2 = 2 * ux * uy + c1, 2 * vxy + c2
         b1, b2 = ux ** 2 + uy ** 2 + c1, vx + vy + c2
         S = (a1 * a2) / (b1 * b2)

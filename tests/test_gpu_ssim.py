@@ -109,13 +109,13 @@ def test_full_map_against_the_fp64_restatement(dev, h, w, c, cin):
         assert err <= bound, (kind, err, bound, np.unravel_index(diff.argmax(), diff.shape))
 
 
-def reference_gradients(x, y, c):
+def reference_gradients(x, y, c, data_range=1.0):
     """d ssim / d x over the first c channels by autograd of ssim_torch, in fp64 and in fp32 (host)."""
     from shacira_amd.wisp.ops.image.metrics import ssim_torch
     out = []
     for dtype in (torch.float64, torch.float32):
         a = torch.from_numpy(x[..., :c]).to(dtype).requires_grad_(True)
-        (g,) = torch.autograd.grad(ssim_torch(a, torch.from_numpy(y[..., :c]).to(dtype)), a)
+        (g,) = torch.autograd.grad(ssim_torch(a, torch.from_numpy(y[..., :c]).to(dtype), data_range=data_range), a)
         out.append(g.double().numpy())
     return out
 

@@ -23,6 +23,53 @@ def test_restatement_is_exactly_one_on_identical_images(dtype):
     assert value == 1.0 and np.all(smap == 1.0)
 
 
+def test_shifted_restatement_is_the_same_definition():
+    """`shift=True` subtracts the channel mean before the fields and adds it back to the means: in fp64 the same numbers on every
+    input kind of the GPU suite, in fp32 the one of the two that keeps its accuracy on a flat image."""
+    from test_gpu_ssim import KINDS, images
+    for h, w in ((11, 11), (27, 75)):
+        for kind in KINDS:
+            x, y = images(kind, h, w, 3)
+            value, smap = ssim_ref.ssim(x, y)
+            shifted_value, shifted_map = ssim_ref.ssim(x, y, shift=True)
+            assert shifted_map.dtype == np.float64 and abs(shifted_value - value) <= 1e-12, kind
+            assert np.abs(shifted_map - smap).max() <= 1e-12, kind
+    x, y = images("flat", 27, 75, 3)
+    _, smap = ssim_ref.ssim(x, y)
+    plain = np.abs(ssim_ref.ssim(x, y, np.float32)[1] - smap).max()
+    shifted_map = ssim_ref.ssim(x, y, np.float32, shift=True)[1]
+    assert shifted_map.dtype == np.float32 and 50 * np.abs(shifted_map - smap).max() < plain
+    a, _ = pair(27, 75, 3)
+    value, smap = ssim_ref.ssim(a, a, np.float32, shift=True)
+    assert value == 1.0 and np.all(smap == 1.0)
+
+
+def test_preconditions_of_the_tile_centre_cases():
+    """tests/test_gpu_ssim_edges.py, B1: every position is the pixel `ssim_stencil_kernel` calls the centre of some tile, the
+    fp64 map is finite wherever the GPU test compares it, and the left-out pixels are few."""
+    import test_gpu_ssim_edges as edges
+    from shacira_amd import _lib
+    from test_gpu_ssim import images
+    th, tw = _lib.SSIM_TILE_H, _lib.SSIM_TILE_W
+    assert len(edges.B1_POSITIONS) == 3 and len(edges.B1_VALUES) == 7
+    for position, (h, w, r, c) in edges.B1_POSITIONS.items():
+        centres = {(min(r0 + th // 2, h - 1), min(c0 + tw // 2, w - 1)) for r0 in range(0, h, th) for c0 in range(0, w, tw)}
+        assert (r, c) in centres, position
+        x0, y0 = images("noise02", h, w, 3)
+        for which in edges.B1_WHICH:
+            for value in edges.B1_VALUES:
+                x, y, window, reach = edges.b1_inputs(position, which, value)
+                for image, base, touched in ((x, x0, which != "y"), (y, y0, which != "x")):
+                    changed = np.argwhere(~((image == base) | (np.isnan(image) & np.isnan(base))))
+                    assert changed.tolist() == ([[r, c, edges.B1_CHANNEL]] if touched else []), (position, which, value)
+                with np.errstate(all="ignore"):
+                    _, smap = ssim_ref.ssim(x, y)
+                keep = ~window if edges.b1_excludes(value) else np.ones_like(window)
+                assert np.isfinite(smap[keep]).all(), (position, which, value)
+                assert window.sum() <= 0.05 * h * w and reach.sum() <= 0.16 * h * w
+                assert window[..., edges.B1_CHANNEL].sum() == window.sum() <= 121 and reach.sum() <= 441
+
+
 def test_window_weights():
     w = ssim_ref.window()
     assert w.shape == (11,) and abs(w.sum() - 1.0) < 1e-15
