@@ -81,6 +81,42 @@ static int build_level_table(int dim, int num_lods, int feature_dim, int bw, con
     return 0;
 }
 
+// What a hash-grid entry point knows once the eight shape arguments every one of them begins with are resolved.
+struct GridCall {
+    LevelTable lt;
+    int dim, dtype;
+    int64_t n;
+    bool sorts;   // the forward cell-sorts this shape, so its plan exists (shacira_hashgrid_plan_bytes > 0): THE rule, once
+};
+enum GridAccept { kShapeOnly, kNoF64, kAnyFloat };   // the scalar types an entry takes; kShapeOnly: judged later or never
+
+// dtype, then the batch size: the second stage of resolve_grid, on its own for the entry that judges other things first
+static int grid_batch_ok(const GridCall &c, GridAccept accept) {
+    if (c.dtype != SHACIRA_F32 && c.dtype != SHACIRA_F16 && !(c.dtype == SHACIRA_F64 && accept == kAnyFloat)) return SHACIRA_EDTYPE;
+    return c.n < 0 ? SHACIRA_EINVAL : 0;
+}
+
+// options snapshot, level table, plan rule; unless kShapeOnly, dtype and batch size. Error codes in the order listed.
+static int resolve_grid(int dim, int64_t num_coords, int num_lods, int feature_dim, int bw, const int32_t *res_host,
+                        int64_t table_rows, int dtype, GridAccept accept, GridCall &c) {
+    options_snapshot();
+    const int rc = build_level_table(dim, num_lods, feature_dim, bw, res_host, table_rows, c.lt);
+    if (rc) return rc;
+    c.dim = dim;
+    c.dtype = dtype;
+    c.n = num_coords;
+    c.sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, c.lt, num_coords);
+    return accept == kShapeOnly ? 0 : grid_batch_ok(c, accept);
+}
+
+// A caller's plan buffer: the plan of a shape whose forward sorts nothing does not exist, so such a buffer is ignored (`plan`
+// is NULL afterwards); one that is used holds sample_plan_bytes.
+template <typename P>
+static int caller_plan(const GridCall &c, P *&plan, size_t plan_bytes) {
+    if (plan != nullptr && !c.sorts) plan = nullptr;
+    return plan != nullptr && plan_bytes < sample_plan_bytes(c.dim, c.n) ? SHACIRA_EWORKSPACE : 0;
+}
+
 }  // namespace shacira
 
 using namespace shacira;
@@ -123,10 +159,10 @@ int shacira_get_option(const char *name) {
 size_t shacira_hashgrid_forward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                 int codebook_bitwidth, const int32_t *resolutions_host,
                                                 int64_t table_rows, int dtype) {
-    options_snapshot();
-    LevelTable lt;
-    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
-    return hashgrid_forward_workspace(dim, dtype, lt, num_coords);
+    GridCall c;
+    if (resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype,
+                     kShapeOnly, c)) return 0;
+    return hashgrid_forward_workspace(dim, dtype, c.lt, num_coords);
 }
 
 int shacira_hashgrid_forward(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
@@ -140,11 +176,10 @@ int shacira_hashgrid_forward(int dim, int64_t num_coords, int num_lods, int feat
 
 size_t shacira_hashgrid_plan_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
                                    const int32_t *resolutions_host, int64_t table_rows, int dtype) {
-    options_snapshot();
-    LevelTable lt;
-    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
-    if (dtype == SHACIRA_F64 || table_rows == 0 || !tiled_supported(dim, dtype, lt, num_coords)) return 0;
-    return sample_plan_bytes(dim, num_coords);
+    GridCall c;
+    if (resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype,
+                     kShapeOnly, c)) return 0;
+    return c.sorts ? sample_plan_bytes(dim, num_coords) : 0;
 }
 
 int shacira_hashgrid_forward_planned(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
@@ -152,44 +187,72 @@ int shacira_hashgrid_forward_planned(int dim, int64_t num_coords, int num_lods, 
                                      const float *coords, const void *codebook, int dtype, void *feats, void *plan,
                                      size_t plan_bytes, int plan_flags, void *workspace, size_t workspace_bytes,
                                      void *stream) {
-    options_snapshot();
-    LevelTable lt;
-    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
-    if (rc) return rc;
-    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16 && dtype != SHACIRA_F64) return SHACIRA_EDTYPE;
-    if (num_coords < 0) return SHACIRA_EINVAL;
+    GridCall c;
+    if (const int rc = resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows,
+                                    dtype, kAnyFloat, c)) return rc;
     if (num_coords == 0) return 0;
     if (!codebook_first_idx || !coords || !codebook || !feats) return SHACIRA_EINVAL;
-    // a plan buffer is used only by the shapes that sort (shacira_hashgrid_plan_bytes > 0); others ignore it
-    const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
-    // (a call that brings its plan buffer needs shacira_hashgrid_plan_bytes less than the workspace query says)
-    const size_t need = hashgrid_forward_workspace(dim, dtype, lt, num_coords, plan != nullptr && sorts);
+    const bool brought = plan != nullptr;   // SHACIRA_PLAN_READY is judged by what the caller brought, used or ignored
+    if (caller_plan(c, plan, plan_bytes)) return SHACIRA_EWORKSPACE;
+    // (a call whose plan buffer is used needs shacira_hashgrid_plan_bytes less than the workspace query says)
+    const size_t need = hashgrid_forward_workspace(dim, dtype, c.lt, num_coords, plan != nullptr);
     if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
-    if (plan != nullptr && sorts && plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
-    if ((plan_flags & ~SHACIRA_PLAN_READY) != 0 || ((plan_flags & SHACIRA_PLAN_READY) != 0 && plan == nullptr)) return SHACIRA_EINVAL;
-    return (int)hashgrid_forward_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, feats, workspace,
-                                          num_coords, (hipStream_t)stream, sorts ? plan : nullptr,
-                                          (plan_flags & SHACIRA_PLAN_READY) != 0);
+    const bool ready = (plan_flags & SHACIRA_PLAN_READY) != 0;
+    if ((plan_flags & ~SHACIRA_PLAN_READY) != 0 || (ready && !brought)) return SHACIRA_EINVAL;
+    return (int)hashgrid_forward_dispatch(dim, dtype, c.lt, codebook_first_idx, coords, codebook, feats, workspace,
+                                          num_coords, (hipStream_t)stream, plan, ready);
 }
 
 int shacira_hashgrid_debug_corners(int dim, int64_t num_coords, int num_lods, int codebook_bitwidth,
                                    const int32_t *resolutions_host, const float *coords, int32_t *corner_rows,
                                    float *corner_weights, void *stream) {
-    LevelTable lt;
-    int rc = build_level_table(dim, num_lods, 2, codebook_bitwidth, resolutions_host, 0, lt);
-    if (rc) return rc;
+    GridCall c;   // (corners depend on no table: two features, no rows, no scalar type)
+    if (const int rc = resolve_grid(dim, num_coords, num_lods, 2, codebook_bitwidth, resolutions_host, 0, SHACIRA_F32,
+                                    kShapeOnly, c)) return rc;
     if (num_coords < 0 || num_coords * (int64_t)num_lods >= ((int64_t)1 << 31) * 256) return SHACIRA_EINVAL;
     if (num_coords > 0 && (!coords || (!corner_rows && !corner_weights))) return SHACIRA_EINVAL;
-    return (int)hashgrid_debug_corners(dim, lt, coords, num_coords, corner_rows, corner_weights, (hipStream_t)stream);
+    return (int)hashgrid_debug_corners(dim, c.lt, coords, num_coords, corner_rows, corner_weights, (hipStream_t)stream);
 }
 
 size_t shacira_hashgrid_backward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                  int codebook_bitwidth, const int32_t *resolutions_host,
                                                  int64_t table_rows, int dtype) {
-    options_snapshot();
-    LevelTable lt;
-    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
-    return hashgrid_backward_workspace(dim, dtype, lt, num_coords);
+    GridCall c;
+    if (resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype,
+                     kShapeOnly, c)) return 0;
+    return hashgrid_backward_workspace(dim, dtype, c.lt, num_coords);
+}
+
+// the body of the three backward entry points
+static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
+                         const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
+                         const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,
+                         int level_end, int flags, const void *plan, size_t plan_bytes, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+    GridCall c;
+    // (kShapeOnly: the level range and its rules are judged before the scalar type)
+    if (const int rc = resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows,
+                                    dtype, kShapeOnly, c)) return rc;
+    if (level_begin < 0 || level_end > num_lods || level_begin >= level_end) return SHACIRA_EINVAL;
+    const bool partial = !(level_begin == 0 && level_end == num_lods);
+    // level ranges: fp32 tables, and (round 4) fp16 tables without the staged-gradient flags -- each call then converts its own
+    // rows of the fp32 accumulation image only; double tables take whole calls
+    if (partial && dtype == SHACIRA_F64) return SHACIRA_EDTYPE;
+    if (dtype == SHACIRA_F16 && (flags & (SHACIRA_BWD_STAGE_ALL_LEVELS | SHACIRA_BWD_REUSE_STAGED)) != 0) return SHACIRA_EDTYPE;
+    c.lt.level_begin = level_begin;
+    c.lt.level_end = level_end;
+    c.lt.stage_flags = flags & (SHACIRA_BWD_STAGE_ALL_LEVELS | SHACIRA_BWD_REUSE_STAGED);
+    if (const int rc = grid_batch_ok(c, kAnyFloat)) return rc;
+    if (!grad_codebook) return SHACIRA_EINVAL;
+    if (num_coords > 0 && (!codebook_first_idx || !coords || !grad_output)) return SHACIRA_EINVAL;
+    if (caller_plan(c, plan, plan_bytes)) return SHACIRA_EWORKSPACE;
+    // a planned call is sized by what it runs: shacira_hashgrid_backward_planned_workspace_bytes when its brick pass takes the
+    // coarse levels (16-byte aligned grad_output), the plain size otherwise. The dispatcher checks it, before it launches
+    // anything, with the call it resolved for the launch.
+    bool too_small = false;
+    const hipError_t e = hashgrid_backward_dispatch(dim, dtype, c.lt, codebook_first_idx, coords, grad_output, grad_codebook,
+                                                    workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan, &too_small);
+    return too_small ? SHACIRA_EWORKSPACE : (int)e;
 }
 
 int shacira_hashgrid_backward(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
@@ -201,22 +264,14 @@ int shacira_hashgrid_backward(int dim, int64_t num_coords, int num_lods, int fea
                                             0, num_lods, 0, workspace, workspace_bytes, stream);
 }
 
-static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
-                         const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
-                         const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,
-                         int level_end, int flags, const void *plan, size_t plan_bytes, void *workspace,
-                         size_t workspace_bytes, void *stream);
-
 size_t shacira_hashgrid_backward_planned_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                          int codebook_bitwidth, const int32_t *resolutions_host,
                                                          int64_t table_rows, int dtype) {
-    options_snapshot();
-    LevelTable lt;
-    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
-    LevelTable full = lt;
-    const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, full, num_coords);
-    if (!sorts) return hashgrid_backward_workspace(dim, dtype, lt, num_coords);   // no plan for this shape: the plain call
-    return hashgrid_backward_workspace_planned(dim, dtype, lt, num_coords, true);
+    GridCall c;
+    if (resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype,
+                     kShapeOnly, c)) return 0;
+    if (!c.sorts) return hashgrid_backward_workspace(dim, dtype, c.lt, num_coords);   // no plan for this shape: the plain call
+    return hashgrid_backward_workspace_planned(dim, dtype, c.lt, num_coords, true);
 }
 
 int shacira_hashgrid_backward_planned(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
@@ -242,8 +297,6 @@ int shacira_hashgrid_backward_levels(int dim, int64_t num_coords, int num_lods, 
 size_t shacira_hashgrid_coords_backward_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                         int codebook_bitwidth, const int32_t *resolutions_host,
                                                         int64_t table_rows, int dtype) {
-    (void)dim; (void)num_coords; (void)num_lods; (void)feature_dim; (void)codebook_bitwidth; (void)resolutions_host;
-    (void)table_rows; (void)dtype;
     return 0;   // every variant is a pure gather (the ABI keeps the argument for later variants)
 }
 
@@ -252,36 +305,32 @@ int shacira_hashgrid_coords_backward(int dim, int64_t num_coords, int num_lods, 
                                      const float *coords, const void *codebook, const void *grad_output, int dtype,
                                      float *grad_coords, const void *plan, size_t plan_bytes, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-    options_snapshot();
-    LevelTable lt;
-    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
-    if (rc) return rc;
-    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16 && dtype != SHACIRA_F64) return SHACIRA_EDTYPE;
-    if (num_coords < 0) return SHACIRA_EINVAL;
+    GridCall c;
+    if (const int rc = resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows,
+                                    dtype, kAnyFloat, c)) return rc;
     if (num_coords == 0) return 0;
     if (!codebook_first_idx || !coords || !codebook || !grad_output || !grad_coords) return SHACIRA_EINVAL;
     const size_t need = shacira_hashgrid_coords_backward_workspace_bytes(dim, num_coords, num_lods, feature_dim,
                                                                          codebook_bitwidth, resolutions_host, table_rows,
                                                                          dtype);
     if (need > 0 && (!workspace || workspace_bytes < need)) return SHACIRA_EWORKSPACE;
-    // the plan of a shape whose forward sorts nothing does not exist: such a buffer is ignored (as in backward_call)
-    if (plan != nullptr) {
-        const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
-        if (!sorts) plan = nullptr;
-        else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
-    }
-    return (int)hashgrid_coord_grad_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, grad_output, grad_coords,
+    if (caller_plan(c, plan, plan_bytes)) return SHACIRA_EWORKSPACE;
+    return (int)hashgrid_coord_grad_dispatch(dim, dtype, c.lt, codebook_first_idx, coords, codebook, grad_output, grad_coords,
                                              num_coords, (hipStream_t)stream, plan);
+}
+
+// fp16 tables: the fp32 image grad_codebook is accumulated in (used only by calls that ask for grad_codebook)
+static size_t coords_backward2_workspace(const GridCall &c) {
+    return c.dtype == SHACIRA_F16 ? (size_t)c.lt.table_rows * (size_t)c.lt.feature_dim * sizeof(float) : 0;
 }
 
 size_t shacira_hashgrid_coords_backward2_workspace_bytes(int dim, int64_t num_coords, int num_lods, int feature_dim,
                                                          int codebook_bitwidth, const int32_t *resolutions_host,
                                                          int64_t table_rows, int dtype) {
-    LevelTable lt;
-    if (build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt)) return 0;
-    (void)num_coords;
-    // fp16 tables: the fp32 image grad_codebook is accumulated in (used only by calls that ask for grad_codebook)
-    return dtype == SHACIRA_F16 ? (size_t)table_rows * (size_t)feature_dim * sizeof(float) : 0;
+    GridCall c;
+    if (resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype,
+                     kShapeOnly, c)) return 0;
+    return coords_backward2_workspace(c);
 }
 
 int shacira_hashgrid_coords_backward2(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
@@ -290,30 +339,19 @@ int shacira_hashgrid_coords_backward2(int dim, int64_t num_coords, int num_lods,
                                       const float *grad_grad_coords, int dtype, void *grad_grad_output, void *grad_codebook,
                                       float *grad_coords, const void *plan, size_t plan_bytes, void *workspace,
                                       size_t workspace_bytes, void *stream) {
-    options_snapshot();
-    LevelTable lt;
-    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
-    if (rc) return rc;
-    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16) return SHACIRA_EDTYPE;   // (fp64 tables included: first order only)
-    if (num_coords < 0) return SHACIRA_EINVAL;
+    GridCall c;   // (kNoF64: double tables are first order only)
+    if (const int rc = resolve_grid(dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows,
+                                    dtype, kNoF64, c)) return rc;
     if (!grad_grad_output && !grad_codebook && !grad_coords) return SHACIRA_EINVAL;
     if (num_coords > 0) {
         if (!codebook_first_idx || !coords || !grad_grad_coords) return SHACIRA_EINVAL;
         if (!codebook && (grad_grad_output || grad_coords)) return SHACIRA_EINVAL;
         if (!grad_output && (grad_codebook || grad_coords)) return SHACIRA_EINVAL;
-        if (grad_codebook && dtype == SHACIRA_F16 && table_rows > 0) {
-            const size_t need = shacira_hashgrid_coords_backward2_workspace_bytes(
-                dim, num_coords, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, dtype);
-            if (!workspace || workspace_bytes < need) return SHACIRA_EWORKSPACE;
-        }
-        // the plan of a shape whose forward sorts nothing does not exist: such a buffer is ignored
-        if (plan != nullptr) {
-            const bool sorts = table_rows > 0 && tiled_supported(dim, dtype, lt, num_coords);
-            if (!sorts) plan = nullptr;
-            else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
-        }
+        if (grad_codebook && dtype == SHACIRA_F16 && table_rows > 0 &&
+            (!workspace || workspace_bytes < coords_backward2_workspace(c))) return SHACIRA_EWORKSPACE;
+        if (caller_plan(c, plan, plan_bytes)) return SHACIRA_EWORKSPACE;
     }
-    return (int)hashgrid_coord_grad2_dispatch(dim, dtype, lt, codebook_first_idx, coords, codebook, grad_output,
+    return (int)hashgrid_coord_grad2_dispatch(dim, dtype, c.lt, codebook_first_idx, coords, codebook, grad_output,
                                               grad_grad_coords, grad_grad_output, grad_codebook, grad_coords, workspace,
                                               num_coords, (hipStream_t)stream, plan);
 }
@@ -976,45 +1014,6 @@ int shacira_sphere_trace_step(int64_t num_packs, int64_t num_nugs, int64_t num_a
                                          dirs, depth, pack_end, pidx, step_size, min_dis, dist_max, t, dist, dist_prev,
                                          curr, x, active, hit, active_out, coords_out, pidx_out, count_out, count_next,
                                          (hipStream_t)stream);
-}
-
-static int backward_call(int dim, int64_t num_coords, int num_lods, int feature_dim, int codebook_bitwidth,
-                         const int32_t *resolutions_host, const int32_t *codebook_first_idx, int64_t table_rows,
-                         const float *coords, const void *grad_output, int dtype, void *grad_codebook, int level_begin,
-                         int level_end, int flags, const void *plan, size_t plan_bytes, void *workspace,
-                         size_t workspace_bytes, void *stream) {
-    options_snapshot();
-    LevelTable lt;
-    int rc = build_level_table(dim, num_lods, feature_dim, codebook_bitwidth, resolutions_host, table_rows, lt);
-    if (rc) return rc;
-    if (level_begin < 0 || level_end > num_lods || level_begin >= level_end) return SHACIRA_EINVAL;
-    const bool partial = !(level_begin == 0 && level_end == num_lods);
-    // level ranges: fp32 tables, and (round 4) fp16 tables without the staged-gradient flags -- each call then converts its own
-    // rows of the fp32 accumulation image only; double tables take whole calls
-    if (partial && dtype == SHACIRA_F64) return SHACIRA_EDTYPE;
-    if (dtype == SHACIRA_F16 && (flags & (SHACIRA_BWD_STAGE_ALL_LEVELS | SHACIRA_BWD_REUSE_STAGED)) != 0) return SHACIRA_EDTYPE;
-    lt.level_begin = level_begin;
-    lt.level_end = level_end;
-    lt.stage_flags = flags & (SHACIRA_BWD_STAGE_ALL_LEVELS | SHACIRA_BWD_REUSE_STAGED);
-    if (dtype != SHACIRA_F32 && dtype != SHACIRA_F16 && dtype != SHACIRA_F64) return SHACIRA_EDTYPE;
-    if (num_coords < 0 || !grad_codebook) return SHACIRA_EINVAL;
-    if (num_coords > 0 && (!codebook_first_idx || !coords || !grad_output)) return SHACIRA_EINVAL;
-    // the plan of a shape whose forward sorts nothing does not exist: such a buffer is ignored
-    if (plan != nullptr) {
-        LevelTable full = lt;
-        full.level_begin = 0;
-        full.level_end = num_lods;
-        const bool sorts = dtype != SHACIRA_F64 && table_rows > 0 && tiled_supported(dim, dtype, full, num_coords);
-        if (!sorts) plan = nullptr;
-        else if (plan_bytes < sample_plan_bytes(dim, num_coords)) return SHACIRA_EWORKSPACE;
-    }
-    // a planned call is sized by what it runs: shacira_hashgrid_backward_planned_workspace_bytes when its brick pass takes the
-    // coarse levels (16-byte aligned grad_output), the plain size otherwise. The dispatcher checks it, before it launches
-    // anything, with the call it resolved for the launch.
-    bool too_small = false;
-    const hipError_t e = hashgrid_backward_dispatch(dim, dtype, lt, codebook_first_idx, coords, grad_output, grad_codebook,
-                                                    workspace, workspace_bytes, num_coords, (hipStream_t)stream, plan, &too_small);
-    return too_small ? SHACIRA_EWORKSPACE : (int)e;
 }
 
 // ---- view shading ---------------------------------------------------------------------------------------------------------------

@@ -160,25 +160,41 @@ def retained_workspace_bytes():
 
 # workspace sizes are pure functions of the shape and the library's tunables: one C call per new shape, not per call
 @functools.lru_cache(maxsize=4096)   # (NeRF steps change N every step: 256 entries thrashed)
-def _ws_bytes(kind, dim, N, L, F, bw, res, T, dt, epoch):
-    fn = (_lib.lib().shacira_hashgrid_forward_workspace_bytes, _lib.lib().shacira_hashgrid_backward_workspace_bytes,
-          _lib.lib().shacira_hashgrid_plan_bytes, _lib.lib().shacira_hashgrid_backward_planned_workspace_bytes)[kind]
-    return int(fn(dim, N, L, F, bw, _res_array(res), T, dt))
+def _grid_bytes(shape, query, epoch):
+    return int(getattr(_lib.lib(), "shacira_hashgrid_" + query)(*shape.head(), shape.T, shape.dt))
+
+
+class _GridShape(collections.namedtuple("_GridShape", "dim N L F bw res T dt")):
+    """What every hash-grid entry point of the C ABI begins with, in that order, built once per operator call (``res``: a tuple)."""
+    __slots__ = ()
+
+    def head(self):
+        """The leading C arguments, up to the resolutions array (``codebook_first_idx`` or ``table_rows`` come next)."""
+        return (*self[:5], _res_array(self.res))
+
+    def bytes(self, query):
+        """``shacira_hashgrid_<query>`` of this shape (a size query), cached per shape and options epoch."""
+        return _grid_bytes(self, query, _lib.options_epoch)
+
+
+def _grid_shape(dim, N, resolution, codebook_bitwidth, T, F, dt):
+    res = tuple(map(int, resolution))
+    # (tuple.__new__, not _GridShape(...): one Python-level call less, on a path whose host cost shows in small batches)
+    return tuple.__new__(_GridShape, (dim, N, len(res), F, int(codebook_bitwidth), res, T, dt))
 
 
 def hashgrid_plan_bytes(dim, num_coords, table_rows, table_dtype, resolution, codebook_bitwidth, feature_dim):
     """Size of the plan buffer the forward of this shape fills (0: it sorts nothing -- pass ``plan=None``)."""
-    res = tuple(int(r) for r in resolution)
-    return _ws_bytes(2, dim, int(num_coords), len(res), int(feature_dim), int(codebook_bitwidth), res, int(table_rows),
-                     _DTYPES[table_dtype], _lib.options_epoch)
+    return _grid_shape(dim, int(num_coords), resolution, codebook_bitwidth, int(table_rows), int(feature_dim),
+                       _DTYPES[table_dtype]).bytes("plan_bytes")
 
 
 def hashgrid_backward_workspace_bytes(dim, num_coords, table_rows, table_dtype, resolution, codebook_bitwidth, feature_dim,
                                       planned=False):
     """Scratch bytes of the backward of this shape; ``planned=True``: of a whole call that brings the batch's plan."""
-    res = tuple(int(r) for r in resolution)
-    return _ws_bytes(3 if planned else 1, dim, int(num_coords), len(res), int(feature_dim), int(codebook_bitwidth), res,
-                     int(table_rows), _DTYPES[table_dtype], _lib.options_epoch)
+    return _grid_shape(dim, int(num_coords), resolution, codebook_bitwidth, int(table_rows), int(feature_dim),
+                       _DTYPES[table_dtype]).bytes("backward_planned_workspace_bytes" if planned
+                                                   else "backward_workspace_bytes")
 
 
 def hashgrid_plan_buffer(dim, coords, codebook, resolution, codebook_bitwidth):
@@ -214,25 +230,22 @@ def _dtype_code(t):
 
 def _hashgrid_forward(dim, coords, codebook, codebook_first_idx, resolution, codebook_bitwidth, plan=None, plan_ready=False):
     _check_float_coords(dim, coords, codebook, codebook_first_idx)
-    res = tuple(int(r) for r in resolution)
-    N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
-    feats = torch.empty((N, F * len(res)), dtype=codebook.dtype, device=codebook.device)
-    dt = _dtype_code(codebook)
+    sh = _grid_shape(dim, coords.shape[0], resolution, codebook_bitwidth, codebook.shape[0], codebook.shape[1],
+                     _dtype_code(codebook))
+    feats = torch.empty((sh.N, sh.F * sh.L), dtype=codebook.dtype, device=codebook.device)
     L = _lib.lib()
     with _on_device(codebook.device):
-        nbytes = _ws_bytes(0, dim, N, len(res), F, int(codebook_bitwidth), res, T, dt, _lib.options_epoch)
+        nbytes = sh.bytes("forward_workspace_bytes")
         if plan is not None:   # the workspace query includes a plan region for calls that bring none (shacira_hip.h)
-            nbytes -= _ws_bytes(2, dim, N, len(res), F, int(codebook_bitwidth), res, T, dt, _lib.options_epoch)
+            nbytes -= sh.bytes("plan_bytes")
         ws = _workspace(codebook.device, nbytes)
         if plan is None:
-            rc = L.shacira_hashgrid_forward(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                            _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook), dt, _ptr(feats),
-                                            _ptr(ws), nbytes, _stream(codebook))
+            rc = L.shacira_hashgrid_forward(*sh.head(), _ptr(codebook_first_idx), sh.T, _ptr(coords), _ptr(codebook),
+                                            sh.dt, _ptr(feats), _ptr(ws), nbytes, _stream(codebook))
         else:
             _need_gpu(plan)
-            rc = L.shacira_hashgrid_forward_planned(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                                    _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook), dt,
-                                                    _ptr(feats), _ptr(plan), plan.numel(),
+            rc = L.shacira_hashgrid_forward_planned(*sh.head(), _ptr(codebook_first_idx), sh.T, _ptr(coords),
+                                                    _ptr(codebook), sh.dt, _ptr(feats), _ptr(plan), plan.numel(),
                                                     _lib.PLAN_READY if plan_ready else 0, _ptr(ws), nbytes,
                                                     _stream(codebook))
     _lib.check(rc, "hashgrid_interpolate")
@@ -251,52 +264,60 @@ def hashgrid_backward(dim, coords, grad_output, table_rows, table_dtype, codeboo
     BWD_REUSE_STAGED on the following ones, so the gradients are transposed once."""
     _need_gpu(coords, grad_output, codebook_first_idx)
     _check_coords(dim, coords)
-    res = tuple(int(r) for r in resolution)
-    N, T, F = coords.shape[0], int(table_rows), int(feature_dim)
     if table_dtype not in _DTYPES:
         raise RuntimeError(f"shacira_amd: unsupported table dtype {table_dtype} (fp32, fp16 and fp64 are implemented)")
-    dt = _DTYPES[table_dtype]
+    sh = _grid_shape(dim, coords.shape[0], resolution, codebook_bitwidth, int(table_rows), int(feature_dim),
+                     _DTYPES[table_dtype])
+    whole = (0, sh.L)
     if grad_output.dtype != table_dtype:
         grad_output = grad_output.to(table_dtype)
     device = grad_output.device
     if out is not None:
-        if tuple(out.shape) != (T, F) or out.dtype != table_dtype or not out.is_contiguous():
+        if tuple(out.shape) != (sh.T, sh.F) or out.dtype != table_dtype or not out.is_contiguous():
             raise RuntimeError("out must be a contiguous [table_rows, feature_dim] tensor of the table dtype")
         grad_codebook = out
     else:
-        if levels is not None and tuple(levels) != (0, len(res)):
+        if levels is not None and tuple(levels) != whole:
             raise RuntimeError("a level range needs an existing `out` buffer (other rows are left untouched)")
-        grad_codebook = torch.empty((T, F), dtype=table_dtype, device=device)
-    lb, le = (0, len(res)) if levels is None else (int(levels[0]), int(levels[1]))
+        grad_codebook = torch.empty((sh.T, sh.F), dtype=table_dtype, device=device)
+    lb, le = whole if levels is None else (int(levels[0]), int(levels[1]))
     L = _lib.lib()
     with _on_device(device):
-        planned = plan is not None and (lb, le) == (0, len(res)) and not flags
+        planned = plan is not None and (lb, le) == whole and not flags
         # (a planned call whose coarse levels go through the brick pass writes fewer, smaller items: its own query -- valid for
         # 16-byte aligned gradients, which every freshly allocated tensor is)
-        kind = 3 if planned and grad_output.data_ptr() % 16 == 0 else 1
-        nbytes = _ws_bytes(kind, dim, N, len(res), F, int(codebook_bitwidth), res, T, dt, _lib.options_epoch)
+        nbytes = sh.bytes("backward_planned_workspace_bytes" if planned and grad_output.data_ptr() % 16 == 0
+                          else "backward_workspace_bytes")
         if workspace is not None:
             if workspace.numel() * workspace.element_size() < nbytes:
                 raise RuntimeError("workspace too small")
             ws = workspace
-        elif levels is not None and tuple(levels) != (0, len(res)):
+        elif levels is not None and tuple(levels) != whole:
             # a level-range call WITHOUT a shared workspace stages nothing for later calls: scratch of its own
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
         else:
             ws = _workspace(device, nbytes)
         if planned:
             _need_gpu(plan)
-            rc = L.shacira_hashgrid_backward_planned(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                                     _ptr(codebook_first_idx), T, _ptr(coords), _ptr(grad_output), dt,
-                                                     _ptr(grad_codebook), _ptr(plan), plan.numel(), _ptr(ws), nbytes,
-                                                     _stream(grad_output))
+            rc = L.shacira_hashgrid_backward_planned(*sh.head(), _ptr(codebook_first_idx), sh.T, _ptr(coords),
+                                                     _ptr(grad_output), sh.dt, _ptr(grad_codebook), _ptr(plan),
+                                                     plan.numel(), _ptr(ws), nbytes, _stream(grad_output))
         else:
-            rc = L.shacira_hashgrid_backward_levels(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                                    _ptr(codebook_first_idx), T, _ptr(coords), _ptr(grad_output), dt,
-                                                    _ptr(grad_codebook), lb, le, int(flags), _ptr(ws), nbytes,
-                                                    _stream(grad_output))
+            rc = L.shacira_hashgrid_backward_levels(*sh.head(), _ptr(codebook_first_idx), sh.T, _ptr(coords),
+                                                    _ptr(grad_output), sh.dt, _ptr(grad_codebook), lb, le, int(flags),
+                                                    _ptr(ws), nbytes, _stream(grad_output))
     _lib.check(rc, "hashgrid_interpolate_backward")
     return grad_codebook
+
+
+def _table_operands(sh, codebook, grad_output):
+    """The coordinate gradients' table and ``grad_output`` [N, L*F]: contiguous, the latter in the table's dtype."""
+    if grad_output.dtype != codebook.dtype:
+        grad_output = grad_output.to(codebook.dtype)
+    grad_output = grad_output.contiguous()
+    if tuple(grad_output.shape) != (sh.N, sh.L * sh.F):
+        raise RuntimeError(f"grad_output must be [{sh.N}, {sh.L * sh.F}], got {tuple(grad_output.shape)}")
+    return codebook.contiguous(), grad_output
 
 
 def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_idx, resolution, codebook_bitwidth,
@@ -305,28 +326,19 @@ def hashgrid_coords_backward(dim, coords, grad_output, codebook, codebook_first_
     shacira_hashgrid_coords_backward). ``codebook`` is the table the forward read; ``grad_output`` [N, L*F] is taken in
     the table's dtype; ``plan``: the buffer the forward of the SAME coordinate batch filled, or None."""
     _check_float_coords(dim, coords, grad_output, codebook, codebook_first_idx)
-    res = tuple(int(r) for r in resolution)
-    N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
-    dt = _dtype_code(codebook)
-    codebook = codebook.contiguous()
-    if grad_output.dtype != codebook.dtype:
-        grad_output = grad_output.to(codebook.dtype)
-    grad_output = grad_output.contiguous()
-    if tuple(grad_output.shape) != (N, len(res) * F):
-        raise RuntimeError(f"grad_output must be [{N}, {len(res) * F}], got {tuple(grad_output.shape)}")
-    grad_coords = torch.empty((N, dim), dtype=torch.float32, device=coords.device)
-    L = _lib.lib()
+    sh = _grid_shape(dim, coords.shape[0], resolution, codebook_bitwidth, codebook.shape[0], codebook.shape[1],
+                     _dtype_code(codebook))
+    codebook, grad_output = _table_operands(sh, codebook, grad_output)
+    grad_coords = torch.empty((sh.N, dim), dtype=torch.float32, device=coords.device)
     with _on_device(coords.device):
-        nbytes = int(L.shacira_hashgrid_coords_backward_workspace_bytes(dim, N, len(res), F, int(codebook_bitwidth),
-                                                                         _res_array(res), T, dt))
+        nbytes = sh.bytes("coords_backward_workspace_bytes")
         ws = _workspace(coords.device, nbytes)
         if plan is not None:
             _need_gpu(plan)
-        rc = L.shacira_hashgrid_coords_backward(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                                _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook),
-                                                _ptr(grad_output), dt, _ptr(grad_coords), _ptr(plan),
-                                                0 if plan is None else plan.numel(), _ptr(ws), nbytes,
-                                                _stream(coords))
+        rc = _lib.lib().shacira_hashgrid_coords_backward(*sh.head(), _ptr(codebook_first_idx), sh.T, _ptr(coords),
+                                                         _ptr(codebook), _ptr(grad_output), sh.dt, _ptr(grad_coords),
+                                                         _ptr(plan), 0 if plan is None else plan.numel(), _ptr(ws), nbytes,
+                                                         _stream(coords))
     _lib.check(rc, "hashgrid_coords_backward")
     return grad_coords
 
@@ -345,40 +357,31 @@ def hashgrid_coords_backward2(dim, coords, grad_output, grad_grad_coords, codebo
     if codebook.dtype not in (torch.float32, torch.float16):
         raise RuntimeError(f"shacira_amd: the second-order hash-grid gradients are implemented for fp32 and fp16 tables, "
                            f"not {codebook.dtype}")
-    res = tuple(int(r) for r in resolution)
-    N, T, F = coords.shape[0], codebook.shape[0], codebook.shape[1]
-    dt = _dtype_code(codebook)
-    device = coords.device
-    codebook = codebook.contiguous()
-    if grad_output.dtype != codebook.dtype:
-        grad_output = grad_output.to(codebook.dtype)
-    grad_output = grad_output.contiguous()
-    if tuple(grad_output.shape) != (N, len(res) * F):
-        raise RuntimeError(f"grad_output must be [{N}, {len(res) * F}], got {tuple(grad_output.shape)}")
+    sh = _grid_shape(dim, coords.shape[0], resolution, codebook_bitwidth, codebook.shape[0], codebook.shape[1],
+                     _dtype_code(codebook))
+    N, T, device = sh.N, sh.T, coords.device
+    codebook, grad_output = _table_operands(sh, codebook, grad_output)
     v = grad_grad_coords
     if v.dtype != torch.float32:
         v = v.float()
     v = v.contiguous()
     if tuple(v.shape) != (N, dim):
         raise RuntimeError(f"grad_grad_coords must be [{N}, {dim}], got {tuple(v.shape)}")
-    ggo = torch.empty((N, len(res) * F), dtype=codebook.dtype, device=device) if want[0] else None
-    gcb = torch.empty((T, F), dtype=codebook.dtype, device=device) if want[1] else None
+    ggo = torch.empty((N, sh.L * sh.F), dtype=codebook.dtype, device=device) if want[0] else None
+    gcb = torch.empty((T, sh.F), dtype=codebook.dtype, device=device) if want[1] else None
     gc = torch.empty((N, dim), dtype=torch.float32, device=device) if want[2] else None
     if N == 0 and (not want[1] or T == 0):     # nothing to compute, no table to zero
         return ggo, gcb, gc
-    L = _lib.lib()
     with _on_device(device):
-        nbytes = 0
-        if want[1]:
-            nbytes = int(L.shacira_hashgrid_coords_backward2_workspace_bytes(dim, N, len(res), F, int(codebook_bitwidth),
-                                                                              _res_array(res), T, dt))
+        nbytes = sh.bytes("coords_backward2_workspace_bytes") if want[1] else 0
         ws = _workspace(device, nbytes)
         if plan is not None:
             _need_gpu(plan)
-        rc = L.shacira_hashgrid_coords_backward2(dim, N, len(res), F, int(codebook_bitwidth), _res_array(res),
-                                                 _ptr(codebook_first_idx), T, _ptr(coords), _ptr(codebook),
-                                                 _ptr(grad_output), _ptr(v), dt, _ptr(ggo), _ptr(gcb), _ptr(gc), _ptr(plan),
-                                                 0 if plan is None else plan.numel(), _ptr(ws), nbytes, _stream(coords))
+        rc = _lib.lib().shacira_hashgrid_coords_backward2(*sh.head(), _ptr(codebook_first_idx), T, _ptr(coords),
+                                                          _ptr(codebook), _ptr(grad_output), _ptr(v), sh.dt, _ptr(ggo),
+                                                          _ptr(gcb), _ptr(gc), _ptr(plan),
+                                                          0 if plan is None else plan.numel(), _ptr(ws), nbytes,
+                                                          _stream(coords))
     _lib.check(rc, "hashgrid_coords_backward2")
     return ggo, gcb, gc
 
@@ -401,12 +404,8 @@ def backward_workspace(dim, num_coords, table_rows, table_dtype, resolution, cod
                        planned=False):
     """Scratch buffer a caller can share between several ``hashgrid_backward(..., levels=...)`` calls; ``planned=True``: the
     (smaller) buffer of whole calls that bring the batch's plan."""
-    res = tuple(int(r) for r in resolution)
-    with _on_device(device):
-        query = (_lib.lib().shacira_hashgrid_backward_planned_workspace_bytes if planned
-                 else _lib.lib().shacira_hashgrid_backward_workspace_bytes)
-        n = query(dim, int(num_coords), len(res), int(feature_dim), int(codebook_bitwidth), _res_array(res),
-                  int(table_rows), _DTYPES[table_dtype])
+    n = hashgrid_backward_workspace_bytes(dim, num_coords, table_rows, table_dtype, resolution, codebook_bitwidth,
+                                          feature_dim, planned)
     return torch.empty((max(n, 1),), dtype=torch.uint8, device=device)
 
 

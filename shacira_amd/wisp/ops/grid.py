@@ -55,8 +55,6 @@ def _forward(ctx, dim, coords, resolutions, codebook_bitwidth, codebook, codeboo
         ctx.save_for_backward(coords, codebook_first_idx)
     ctx.plan = plan
     ctx.resolutions = resolutions
-    ctx.num_lods = len(resolutions)
-    ctx.codebook_size = 2 ** codebook_bitwidth
     ctx.codebook_bitwidth = codebook_bitwidth
     ctx.feature_dim = codebook.shape[-1]
     ctx.table_rows = codebook.shape[0]

@@ -164,3 +164,86 @@ def test_backward_workspace_bytes_match_the_recorded_counts(golden):
             for name, value in saved.items():
                 _lib.set_option(name, value)
     assert not bad, (len(bad), bad[:8])
+
+
+def _entry_golden():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_hashgrid_entry_golden as mk
+    return mk
+
+
+def test_hashgrid_size_queries_match_the_recorded_counts(golden):
+    """The forward workspace, plan and coordinate-gradient workspace queries over tables x batch sizes x fp32 / fp16 / fp64 x
+    the options the plan rule reads equal, byte for byte, what tests/golden/make_hashgrid_entry_golden.py recorded before the
+    entry points' shape resolver was gathered into one function (the backward queries: the test above)."""
+    mk = _entry_golden()
+    g = golden("hashgrid_entry_codes.json")
+    assert g["option_sets"] == mk.OPTION_SETS and len(g["option_sets"]) == 7
+    assert len(g["sizes"]) == len(g["tables"]) * 9 * 3 * 7 and set(g["tables"]) == {"A", "B", "Bp", "D", "lego", "tiny"}
+    assert any(r[5] > 0 for r in g["sizes"]) and any(r[4] > 0 and r[5] == 0 for r in g["sizes"])
+    got = mk.query_sizes(g["tables"], sorted({r[1] for r in g["sizes"]}), g["option_sets"])
+    bad = [(a, b) for a, b in zip(sorted(g["sizes"]), sorted(got)) if a != b]
+    assert len(got) == len(g["sizes"]) and not bad, (len(bad), bad[:8])
+
+
+def test_hashgrid_entry_codes_match_the_recorded_codes(golden):
+    """Every single fault and every pair of faults the eight launching hash-grid entries can carry returns the code recorded
+    from the library as it stood before the shape resolver (tests/golden/make_hashgrid_entry_golden.py): which check fires, and
+    which fires FIRST. Every case is refused before dispatch (the addresses are made up), so nothing here touches a GPU -- and
+    where one is present the test does not run at all: a wrongly accepted call would launch on those addresses."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("made-up addresses: replayed only where a wrongly accepted call cannot launch")
+    mk = _entry_golden()
+    g = golden("hashgrid_entry_codes.json")
+    assert g["batches"] == mk.BATCHES and sorted(g["codes"]) == sorted(mk.ENTRIES) and len(mk.ENTRIES) == 8
+    bad, total = [], 0
+    for entry, per in g["codes"].items():
+        for bname, rec in per.items():
+            names = list(mk.faults(entry, g["batches"][bname]))
+            assert names == rec["faults"], (entry, bname)
+            want = {(i, None): c for i, c in enumerate(rec["single"])}
+            want.update({(i, j): c for i, j, c in rec["pairs"]})
+            cases = mk.cases(entry, g["batches"][bname])
+            assert sorted(want, key=str) == sorted(((i, j) for i, j, _ in cases), key=str), (entry, bname)
+            for i, j, args in cases:
+                code = want[(i, j)]
+                assert code < 0 or (code == 0 and entry in mk.ZERO_BATCH_RETURNS_0 and "n0" in (names[i], j is not None and names[j]))
+                got = mk.call(entry, args)
+                total += 1
+                if got != code:
+                    bad.append((entry, bname, names[i], None if j is None else names[j], code, got))
+    assert total > 3000 and not bad, (len(bad), bad[:8])
+
+
+def test_cached_size_queries_equal_the_c_queries_and_follow_the_options():
+    """hip_ops' cached size queries answer what the C queries answer, and the cache is keyed by the options epoch: a shape
+    that has a plan has none once `tiled` is 0, and has it again once the option is restored."""
+    import torch
+    from conftest import CONFIGS, geo, table_layout
+    from shacira_amd import hip_ops
+    L = _lib.lib()
+    tables = {"B": CONFIGS["B"] + (2,), "D": CONFIGS["D"] + (2,), "lego": (3, geo(16, 512, 24), 19, 4)}
+    some_plan = None
+    for dim, res, bw, F in tables.values():
+        arr = (ctypes.c_int32 * len(res))(*res)
+        _, _, T = table_layout(res, bw, dim)
+        for n in (4096, 1 << 18, 1 << 20):
+            c = (dim, n, len(res), F, bw, arr, T, _lib.F32)
+            py = (dim, n, T, torch.float32, res, bw, F)
+            assert hip_ops.hashgrid_plan_bytes(*py) == L.shacira_hashgrid_plan_bytes(*c)
+            assert hip_ops.hashgrid_backward_workspace_bytes(*py) == L.shacira_hashgrid_backward_workspace_bytes(*c)
+            assert hip_ops.hashgrid_backward_workspace_bytes(*py, planned=True) == \
+                L.shacira_hashgrid_backward_planned_workspace_bytes(*c)
+            if L.shacira_hashgrid_plan_bytes(*c) > 0:
+                some_plan = py
+    before = hip_ops.hashgrid_plan_bytes(*some_plan)
+    assert before > 0
+    saved = _lib.get_option("tiled")
+    _lib.set_option("tiled", 0)
+    try:
+        assert hip_ops.hashgrid_plan_bytes(*some_plan) == 0
+    finally:
+        _lib.set_option("tiled", saved)
+    assert hip_ops.hashgrid_plan_bytes(*some_plan) == before
